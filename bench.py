@@ -19,9 +19,14 @@ its per-rank decode gains do not make up for it. `--tp T` runs T-way tensor-para
 overlapped with the next micro-batch in prefill; BASELINE config 3 is `--tp 8`), tp x dp layouts
 for T < N.
 
-value = total generated tokens of all ranks / max-over-ranks wall time of the K timed steps.
-p50_latency_ms is the wave latency of a step; p50_latency_c1_ms the single-query latency (C=1,
-measured after the timed steps: the reference serves one query per /generate call).
+value = total generated tokens of all ranks / max-over-ranks wall time of the K timed steps;
+ms_per_step is that wall time / K. p50_latency_ms is the wave latency of a step.
+
+A plain run does only that: set up, warm up, time the K steps, print the JSON line. `--full` adds the
+measurements that take runs of their own after the timed steps: p50_latency_c1_ms, the single-query
+latency (C=1: the reference serves one query per /generate call), and for N > 1 data-parallel runs the
+C=1 latency of one TP=N engine over every GPU. `--dump-outputs DIR` writes what the last timed step
+returned to its caller as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -62,11 +67,16 @@ def parse():
                     help="linear-layer weights: bf16 (headline) or fp8 e4m3 (BASELINE config 5)")
     ap.add_argument("--seq-parallel", action="store_true",
                     help="TP prefill with Megatron sequence parallelism (reduce-scatter/all-gather)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the C=1 queries (--c1) and the TP=N "
+                         "C=1 phase (--c1-tp) after the timed steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32)")
     ap.add_argument("--c1", type=int, default=5,
-                    help="after the timed steps: this many single queries one at a time (C=1 latency; untimed)")
+                    help="--full: after the timed steps, this many single queries one at a time (C=1 latency; untimed)")
     ap.add_argument("--c1-tp", type=int, default=3,
-                    help="N > 1 data-parallel runs: after the headline, this many C=1 queries on ONE TP=N engine "
-                         "spanning every GPU (untimed; p50_latency_c1_tp_ms, the xGMI latency path); 0 = skip")
+                    help="--full, N > 1 data-parallel runs: after the headline, this many C=1 queries on ONE TP=N "
+                         "engine spanning every GPU (untimed; p50_latency_c1_tp_ms, the xGMI latency path); 0 = skip")
     ap.add_argument("--c1-tp-timeout", type=float, default=float(os.environ.get("RAGK_BENCH_TP_TIMEOUT", "420")),
                     help="seconds the TP=N C=1 phase may take before the headline line is printed without it")
     ap.add_argument("--json-out", default=None)
@@ -81,6 +91,38 @@ def pct(xs, p):
     f = int(k)
     c = min(f + 1, len(xs) - 1)
     return xs[f] + (xs[c] - xs[f]) * (k - f)
+
+
+def _utf8_rows(texts):
+    """Strings as one float32 array [len(texts), longest]: UTF-8 byte values, rows padded with -1."""
+    import numpy as np
+
+    rows = [np.frombuffer(t.encode("utf-8"), dtype=np.uint8) for t in texts]
+    out = np.full((len(rows), max([len(r) for r in rows] + [1])), -1.0, dtype=np.float32)
+    for i, r in enumerate(rows):
+        out[i, :len(r)] = r
+    return out
+
+
+def dump_outputs(out_dir, outs):
+    """What generate_batch returned for the last timed step (one row per query, in query order), as float32
+    .npy files: the answer and the retrieved context as UTF-8 byte values (-1 = padding), and the prompt /
+    generated token counts. The queries and sampling seeds of a step depend only on the arguments, so two
+    builds run with the same arguments can be compared file by file. ~5 MB at the default sizes."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {
+        "generated_text_utf8": _utf8_rows([o.get("generated_text") or "" for o in outs]),
+        "context_utf8": _utf8_rows([o.get("context") or "" for o in outs]),
+        "prompt_tokens": np.array([o.get("_prompt_tokens", 0) for o in outs], dtype=np.float32),
+        "gen_tokens": np.array([o.get("_gen_tokens", 0) for o in outs], dtype=np.float32),
+    }
+    cap = (64 << 20) // len(arrays)  # bytes per file: 64 MB in all
+    for name, arr in arrays.items():
+        if arr.ndim == 2 and arr.nbytes > cap:  # far larger --concurrency / --chunk-words: the head of each row
+            arr = arr[:, :max(1, cap // (4 * arr.shape[0]))]
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def tp_c1_phase(a, ctx, params):
@@ -184,6 +226,7 @@ def main():
     sync()
     t0 = time.perf_counter()
     lat, ttft, ptoks, gtoks, step_ms = [], [], [], [], []
+    outs = None
     for s in range(a.steps):
         ts = time.perf_counter()
         outs = run_step(s)
@@ -197,10 +240,14 @@ def main():
     sync()
     D.barrier(ctx)
     elapsed = time.perf_counter() - t0
-    # single-request latency (the reference serves one query per /generate call): outside the timed
-    # region, same service path, one query at a time
+    if a.dump_outputs and ctx.rank == 0:
+        if outs is None:
+            raise SystemExit("bench.py: --dump-outputs needs at least one timed step")
+        dump_outputs(a.dump_outputs, outs)
+    # --full: single-request latency (the reference serves one query per /generate call): outside the
+    # timed region, same service path, one query at a time
     c1_lat, c1_ttft = [], []
-    for i in range(a.c1):
+    for i in range(a.c1 if a.full else 0):
         q = make_queries(wl.wm, 1, seed=777000 + 1000 * ctx.dp_rank + i)
         o = svc.generate_batch(q, params=params, seeds=[4242 + i])[0]
         if "_latency_s" in o:
@@ -227,8 +274,9 @@ def main():
             "n_gpus": ctx.world,
             "steps": a.steps,
             "warmup": a.warmup,
-            "ms_per_step": round(elapsed_max / a.steps * 1e3, 2),
+            "ms_per_step": round(elapsed_max / max(1, a.steps) * 1e3, 2),
             "higher_is_better": True,
+            "full": a.full,
             "scaling": "weak",
             "vs_baseline": None,
             "dtype": "bf16" if a.dtype == "bf16" else "fp8-weights (bf16 activations/KV)",
@@ -252,14 +300,15 @@ def main():
             "p50_latency_ms": round(pct(L, 50), 1) if L else None,
             "p90_latency_ms": round(pct(L, 90), 1) if L else None,
             "ttft_p50_ms": round(pct(T, 50), 1) if T else None,
-            "p50_latency_c1_ms": round(pct(allstats[0]["c1"], 50), 1) if allstats[0]["c1"] else None,
-            "ttft_c1_p50_ms": round(pct(allstats[0]["c1_ttft"], 50), 1) if allstats[0]["c1_ttft"] else None,
             "per_gpu_tokens_per_s": round(value / ctx.world, 2),
             "engine": {k: (round(v, 3) if isinstance(v, float) else v) for k, v in eng.items()},
             "setup_s": round(setup_s, 1),
             # ingest throughput of the corpus build (tokenize + batched varlen encoder, one GPU)
             "ingest_embed_chunks_per_s": round(a.chunks / max(1e-9, allstats[0]["setup"].get("embed_s", 0.0)), 1),
         }
+        if a.full:
+            res["p50_latency_c1_ms"] = round(pct(allstats[0]["c1"], 50), 1) if allstats[0]["c1"] else None
+            res["ttft_c1_p50_ms"] = round(pct(allstats[0]["c1_ttft"], 50), 1) if allstats[0]["c1_ttft"] else None
     else:
         res = None
 
@@ -272,10 +321,11 @@ def main():
 
     # TP=N C=1 latency over every GPU of the job (after the headline; never changes `value`). At N = 1
     # (or when the headline engine already spans the job) the headline's own C=1 is that number.
-    if ctx.tp == ctx.world or a.c1_tp <= 0:
+    if not a.full or ctx.tp == ctx.world or a.c1_tp <= 0:
         if res is not None:
-            res["p50_latency_c1_tp_ms"] = res["p50_latency_c1_ms"] if ctx.tp == ctx.world else None
-            res["c1_tp_degree"] = ctx.tp
+            if a.full:
+                res["p50_latency_c1_tp_ms"] = res["p50_latency_c1_ms"] if ctx.tp == ctx.world else None
+                res["c1_tp_degree"] = ctx.tp
             emit(res)
         D.shutdown(ctx)
         return
