@@ -23,6 +23,7 @@
 // Replaces reference ops K5/K6 (causal GQA attention in transformers' Llama SDPA path,
 // [dep] modeling_llama.py:191-215) and E3 (XLM-R/BERT bidirectional attention).
 #include "common.h"
+#include "kv_fp8.h"
 #include <type_traits>
 using namespace ragk;
 
@@ -118,6 +119,40 @@ __device__ __forceinline__ bf16x8 pack_p(const f32x4& a, const f32x4& b) {
                   f2bf_s(b[0]), f2bf_s(b[1]), f2bf_s(b[2]), f2bf_s(b[3])};
 }
 
+// ---- fp8 KV cache (kv_fp8.h), D = 128 -------------------------------------------------
+// A 64-row fp8 tile is 64 rows of 128 bytes: the byte geometry of a bf16 D = 64 tile, so K tiles are staged
+// and read with the Cfg<64> piece / swizzle arithmetic (stage_kv<64>, load_k<64>). One 16-byte K read is two
+// 8-value MFMA fragments, so the d order of the QK^T k-steps is permuted (the same on the Q side, f8_qoff):
+// k-step s of lane group fh covers d = 64 (s / 2) + 16 fh + 8 (s % 2) + [0, 8).
+// V tiles are converted on the way in: 16-byte global loads to registers, fp8 -> bf16 (exact), written to
+// LDS in the bf16 Cfg<128> V layout, so PV keeps the ds_read_b64_tr_b16 path (load_vt<128>) unchanged.
+constexpr int F8_D = 128;
+constexpr int F8_TILEB = KT * F8_D;  // bytes of one fp8 K or V tile
+
+__device__ __forceinline__ int f8_qoff(int s, int fh) { return 64 * (s >> 1) + 16 * fh + 8 * (s & 1); }
+
+template <bool NT>
+__device__ __forceinline__ u32x4 f8_ld16(const unsigned char* p) {
+  if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
+  else return *reinterpret_cast<const u32x4*>(p);
+}
+
+// 16-byte chunk `ci` (0..511: row ci / 8, bytes 16 (ci % 8) + [0, 16)) of an fp8 V tile -> the bf16 V tile in LDS
+__device__ __forceinline__ void f8_v_to_lds(char* sV, int ci, const u32x4 raw) {
+  const int row = ci >> 3, c = ci & 7;
+  // logical 16-B chunks 2c, 2c + 1 of the bf16 row; vswz is even, so they stay adjacent
+  char* p = sV + row * Cfg<F8_D>::ROWB + 16 * ((2 * c) ^ vswz<F8_D>(row));
+  *reinterpret_cast<bf16x8*>(p) = kv8_to_bf16(raw[0], raw[1]);
+  *reinterpret_cast<bf16x8*>(p + 16) = kv8_to_bf16(raw[2], raw[3]);
+}
+
+// K fragments of k-steps 2j, 2j + 1 (f8_qoff order) for key rows 16 t + (lane & 15) from an fp8 K tile in LDS
+__device__ __forceinline__ void f8_load_k(const char* sK, int t, int j, int lane, bf16x8& k0, bf16x8& k1) {
+  const u32x4 raw = __builtin_bit_cast(u32x4, load_k<64>(sK, t, j, lane));
+  k0 = kv8_to_bf16(raw[0], raw[1]);
+  k1 = kv8_to_bf16(raw[2], raw[3]);
+}
+
 // ------------------------------------------------------------------------------------
 // Prefill / encoder attention
 // ------------------------------------------------------------------------------------
@@ -135,6 +170,7 @@ struct PrefillArgs {
   float scale_log2;
   unsigned kv_bytes;                       // PAGED: bytes of one cache (K or V) if < 4 GiB, else 0
   int n_hg;                                // > 0: 1-D grid of n_tiles x n_hg, head group fastest
+  const float* ks; const float* vs;        // fp8 cache (F8 kernels): row scales [nblocks][Hkv][64]; k / v = e4m3 bytes
 };
 
 // Prefill block -> (tile index, head group). 1-D grid, head group fastest (n_hg > 0, the default): the
@@ -161,9 +197,13 @@ __device__ unsigned long long* g_attn_dbg = nullptr;  // stamp build only
 // offsets (row, swizzled chunk) computed once and the tile's cache offset in an SGPR, instead of
 // 64-bit address math per piece per tile (the stamp build put the DMA issue at ~490 of ~4300 wave
 // cycles per tile).
+// F8 (PAGED, D = 128): fp8 cache. K tiles by LDS-DMA in the Cfg<64> byte geometry, V tiles through registers
+// into the bf16 V layout (issued with the K DMA, converted and written after the PV MFMAs), the tile's 64 + 64
+// row scales through LDS; S *= ks[key] before the softmax, P *= vs[key] after the row sum.
 template <int D, int GB, bool CAUSAL, bool PAGED, bool STAMP = false, int NWV = 4, int PRIO = 0,
-          bool BUF = false>
+          bool BUF = false, bool F8 = false>
 __global__ __launch_bounds__(NWV * 64, 8 / NWV) void attn_prefill_kernel(PrefillArgs a) {
+  static_assert(!F8 || (PAGED && D == F8_D && !BUF), "fp8 cache: paged, D = 128");
   unsigned long long stp[6] = {0, 0, 0, 0, 0, 0};
   using C = Cfg<D>;
   constexpr int NTH = NWV * 64;
@@ -203,7 +243,8 @@ __global__ __launch_bounds__(NWV * 64, 8 / NWV) void attn_prefill_kernel(Prefill
     qi = qi < q_len ? qi : q_len - 1;
     const bf16_t* qp = a.q + (size_t)(q_off + qi) * a.q_stride + hq * D + 8 * fh;
 #pragma unroll
-    for (int s = 0; s < C::KS; ++s) qf[qt][s] = *reinterpret_cast<const bf16x8*>(qp + 32 * s);
+    for (int s = 0; s < C::KS; ++s)
+      qf[qt][s] = *reinterpret_cast<const bf16x8*>(F8 ? qp - 8 * fh + f8_qoff(s, fh) : qp + 32 * s);
   }
 
   f32x4 o[C::DT][2];
@@ -240,10 +281,33 @@ __global__ __launch_bounds__(NWV * 64, 8 / NWV) void attn_prefill_kernel(Prefill
     srd_k = make_srd(a.k, a.kv_bytes);
     srd_v = make_srd(a.v, a.kv_bytes);
   }
+  // F8: the V chunks and scales of the tile being staged, held in registers from stage() to commit()
+  constexpr int VPT = F8 ? 512 / NTH : 1;  // 16-byte V chunks per thread
+  __shared__ __attribute__((aligned(16))) float s_sc[F8 ? 4 * KT : 4];  // [buf][K | V][64]
+  u32x4 f8_v[VPT];
+  float f8_sc = 0.f;
+  auto commit = [&](int buf) {
+    if constexpr (F8) {
+      char* sV = smem + buf * 2 * C::TILEB + C::TILEB;
+#pragma unroll
+      for (int i = 0; i < VPT; ++i) f8_v_to_lds(sV, (int)threadIdx.x + NTH * i, f8_v[i]);
+      if (threadIdx.x < 2 * KT) s_sc[buf * 2 * KT + threadIdx.x] = f8_sc;
+    }
+  };
   auto stage = [&](int kt, int buf) {
     char* sK = smem + buf * 2 * C::TILEB;
     char* sV = sK + C::TILEB;
-    if constexpr (BUF) {
+    if constexpr (F8) {
+      const size_t blk = (size_t)bt_next * a.Hkv + kvh;
+      const unsigned char* kb = reinterpret_cast<const unsigned char*>(a.k) + blk * F8_TILEB;
+      const unsigned char* vb = reinterpret_cast<const unsigned char*>(a.v) + blk * F8_TILEB;
+      stage_kv<64, false, false, NWV>(sK, wid_u, NWV, lane,
+                                      [&](int r) { return reinterpret_cast<const bf16_t*>(kb + (size_t)r * F8_D); });
+#pragma unroll
+      for (int i = 0; i < VPT; ++i) f8_v[i] = f8_ld16<false>(vb + 16 * ((int)threadIdx.x + NTH * i));
+      if (threadIdx.x < 2 * KT)
+        f8_sc = (threadIdx.x < KT ? a.ks : a.vs)[blk * KT + (threadIdx.x & (KT - 1))];
+    } else if constexpr (BUF) {
       // unsigned: a cache of 2-4 GiB has tile offsets past INT_MAX (soffset is an unsigned 32-bit add)
       const int soff = __builtin_amdgcn_readfirstlane((int)((unsigned)(bt_next * a.Hkv + kvh) * (unsigned)(KT * D * 2)));
 #pragma unroll
@@ -270,7 +334,10 @@ __global__ __launch_bounds__(NWV * 64, 8 / NWV) void attn_prefill_kernel(Prefill
     }
   };
 
-  if (n_kt > 0) stage(0, 0);
+  if (n_kt > 0) {
+    stage(0, 0);
+    commit(0);
+  }
   if constexpr (PAGED) bt_next = n_kt > 1 ? s_bt[1] : 0;
   wait_vmcnt0();
   __syncthreads();
@@ -293,7 +360,14 @@ __global__ __launch_bounds__(NWV * 64, 8 / NWV) void attn_prefill_kernel(Prefill
         s[t][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < C::KS; ++ks) {
-          const bf16x8 kf = load_k<D>(sK, t, ks, lane);
+          bf16x8 kf;
+          if constexpr (F8) {
+            bf16x8 kf1;
+            f8_load_k(sK, t, ks >> 1, lane, kf, kf1);  // one 16-byte read per pair of k-steps (CSE'd)
+            kf = (ks & 1) ? kf1 : kf;
+          } else {
+            kf = load_k<D>(sK, t, ks, lane);
+          }
           s[t][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[0][ks], s[t][0], 0, 0, 0);
           s[t][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[1][ks], s[t][1], 0, 0, 0);
         }
@@ -307,6 +381,17 @@ __global__ __launch_bounds__(NWV * 64, 8 / NWV) void attn_prefill_kernel(Prefill
     if constexpr (PAGED) bt_next = kt + 2 < n_kt ? s_bt[kt + 2] : 0;  // consumed next iteration
     if constexpr (STAMP) t2 = t3 = t4 = __builtin_amdgcn_s_memtime();
     if (active) {
+      f32x4 vsc[4];  // F8: V row scales of this lane's 16 keys
+      if constexpr (F8) {
+        const float* sc = s_sc + cur * 2 * KT + 4 * fh;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const f32x4 kq = *reinterpret_cast<const f32x4*>(sc + 16 * t);
+          vsc[t] = *reinterpret_cast<const f32x4*>(sc + KT + 16 * t);
+          s[t][0] *= kq;
+          s[t][1] *= kq;
+        }
+      }
       // ---- online softmax (per query column, lane-local + xor 16/32) ----
       // Max on the raw scores (scale > 0 keeps the order); the log2 scale is folded into one FMA
       // per element. Deferred rescale: the reference max m_i only moves when the tile max exceeds
@@ -348,7 +433,12 @@ __global__ __launch_bounds__(NWV * 64, 8 / NWV) void attn_prefill_kernel(Prefill
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[t][qt][r], c, -mref));
-            s[t][qt][r] = p;
+            if constexpr (F8) {  // the row sum takes the unscaled p; slots past kv_len may hold any scale bits
+              const bool live = !MASK || k0 + 16 * t + 4 * fh + r < kv_len;
+              s[t][qt][r] = live ? p * vsc[t][r] : 0.f;
+            } else {
+              s[t][qt][r] = p;
+            }
             ls += p;
           }
         l_i[qt] = l_i[qt] * alpha[qt] + ls;
@@ -385,6 +475,7 @@ __global__ __launch_bounds__(NWV * 64, 8 / NWV) void attn_prefill_kernel(Prefill
       if constexpr (PRIO != 0) __builtin_amdgcn_s_setprio(0);
       if constexpr (STAMP) t4 = __builtin_amdgcn_s_memtime();
     }
+    if (kt + 1 < n_kt) commit(cur ^ 1);
     wait_vmcnt0();
     __syncthreads();
     if constexpr (STAMP) {
@@ -942,6 +1033,8 @@ struct DecodeArgs {
   const float* qkv_p; long long p_slab; int ldp, S;
   const int* positions; const int* slots;
   const float* cos_t; const float* sin_t;
+  // fp8 cache (F8 kernels): kc / vc hold e4m3 bytes, ks / vs the fp32 row scales [nblocks][Hkv][64]
+  const float* ks; const float* vs;
 };
 
 // Tiles per partition of one sequence: its KV tiles spread evenly over all max_parts partitions
@@ -955,8 +1048,10 @@ __device__ __forceinline__ int decode_part_tiles(int n_kt, const DecodeArgs& a) 
 
 // LDS of one decode-attention block: one V tile per wave (KL: and one K tile per wave after them), then the
 // block's rotated q (G x D bf16).
-template <int D, int G, int NW = 4, bool KL = false>
-constexpr int decode_lds_bytes() { return NW * Cfg<D>::TILEB * (KL ? 2 : 1) + G * D * 2; }
+template <int D, int G, int NW = 4, bool KL = false, bool F8 = false>
+constexpr int decode_lds_bytes() {
+  return F8 ? NW * (Cfg<D>::TILEB + (KL ? F8_TILEB : 0)) + G * D * 2 : NW * Cfg<D>::TILEB * (KL ? 2 : 1) + G * D * 2;
+}
 
 // One split-K partition block of decode attention: partition `part` of KV head `kvh` of sequence `b`.
 // NW: waves per block (4; 8 for the batch-32 grid with one partition per sequence: one 8-wave block per
@@ -969,11 +1064,16 @@ constexpr int decode_lds_bytes() { return NW * Cfg<D>::TILEB * (KL ? 2 : 1) + G 
 // KL: K tiles arrive by LDS-DMA too (whole 1 KiB pieces instead of 64-B row pieces per lane: the pure access
 // pattern streams 4-5 % faster, tools/attn_decode_probe.py) and the QK^T fragments are read from LDS; a
 // wave then holds 32 KB of LDS, so the single-partition grid uses 4-wave blocks (one per CU).
-template <int D, int G, bool NT = false, int NW = 4, int DG = 0, bool KL = false>
+// F8 (D = 128): fp8 cache. Per tile a wave loads its 64 K and 64 V row scales (256 bytes each), K as 16-byte
+// pieces (registers, or LDS-DMA in the Cfg<64> byte geometry with KL) and V as 16-byte pieces into registers;
+// V is converted to the bf16 V tile in the wave's LDS after the softmax. S *= ks[key] before the softmax,
+// P *= vs[key] after the row sum; the fused append quantizes the new k / v row (kv8_store_row128).
+template <int D, int G, bool NT = false, int NW = 4, int DG = 0, bool KL = false, bool F8 = false>
 __device__ __forceinline__ void attn_decode_block(const DecodeArgs& a, int part, int kvh, int b, char* smem) {
   constexpr int NTH = NW * 64;
   using C = Cfg<D>;
   static_assert(G <= 16, "at most 16 query heads per KV head");
+  static_assert(!F8 || (D == F8_D && DG == 0), "fp8 cache: D = 128");
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int wid_u = __builtin_amdgcn_readfirstlane(wid);
   const int kv_len = a.kv_lens[b];
@@ -992,8 +1092,8 @@ __device__ __forceinline__ void attn_decode_block(const DecodeArgs& a, int part,
   // of following them -- at batch 1 a wave handles a single tile and the two latencies were in series.
   // Not for the sequence's last tile: the new token's k / v is appended into it during the prologue.
   char* sV = smem + wid * C::TILEB;
-  char* sK = smem + (NW + wid) * C::TILEB;  // KL only
-  const bool pre = a.qkv_p != nullptr && kt0 + wid_u < kt1 && kt0 + wid_u != n_kt - 1;  // wave-uniform
+  char* sK = F8 ? smem + NW * C::TILEB + wid * F8_TILEB : smem + (NW + wid) * C::TILEB;  // KL only
+  const bool pre = !F8 && a.qkv_p != nullptr && kt0 + wid_u < kt1 && kt0 + wid_u != n_kt - 1;  // wave-uniform
   bf16x8 kf0[4][C::KS];
   if (pre) {
     const size_t base = ((size_t)bt[kt0 + wid_u] * a.Hkv + kvh) * KT * D;
@@ -1015,7 +1115,7 @@ __device__ __forceinline__ void attn_decode_block(const DecodeArgs& a, int part,
     // pair of 8-vectors per thread (G * D/16 threads, all slab loads of a thread in flight together),
     // staged through LDS; in the block owning the last KV tile, other threads append the new
     // token's k (rotated) and v meanwhile. One barrier covers both.
-    bf16_t* s_q = reinterpret_cast<bf16_t*>(smem + NW * C::TILEB * (KL ? 2 : 1));
+    bf16_t* s_q = reinterpret_cast<bf16_t*>(smem + decode_lds_bytes<D, G, NW, KL, F8>() - G * D * 2);
     constexpr int NV = D / 16;  // pairs per head
     const int pos = a.positions[b];
     const float* prow = a.qkv_p + (size_t)b * a.ldp;
@@ -1040,7 +1140,19 @@ __device__ __forceinline__ void attn_decode_block(const DecodeArgs& a, int part,
       float x1[8], x2[8];
       sum_partials8x2(ph, ph + D / 2, a.S, (size_t)a.p_slab, x1, x2);
       bf16_t* dst = (isv ? const_cast<bf16_t*>(a.vc) : const_cast<bf16_t*>(a.kc)) + kvo;
-      if (isv) {
+      if constexpr (F8) {
+        // lanes [0, NV) of this wave hold the k row, [NV, 2 NV) the v row (NV = 8): amax across each group
+        float r1[8], r2[8];
+        if (isv) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) { r1[e] = x1[e]; r2[e] = x2[e]; }
+        } else {
+          rope8(x1, x2, ct + 8 * v, st + 8 * v, r1, r2);
+        }
+        // one byte per element: the row's byte offset is its element offset kvo, its scale index kvo / D
+        unsigned char* base8 = reinterpret_cast<unsigned char*>(const_cast<bf16_t*>(isv ? a.vc : a.kc));
+        kv8_store_row128(r1, r2, v, base8 + kvo, const_cast<float*>(isv ? a.vs : a.ks) + kvo / D);
+      } else if (isv) {
         *reinterpret_cast<u32x4*>(dst + 8 * v) = pack8(x1);
         *reinterpret_cast<u32x4*>(dst + D / 2 + 8 * v) = pack8(x2);
       } else {
@@ -1053,14 +1165,14 @@ __device__ __forceinline__ void attn_decode_block(const DecodeArgs& a, int part,
     __syncthreads();  // q in LDS; the appended row visible to every wave of this block (same CU)
 #pragma unroll
     for (int s = 0; s < C::KS; ++s)
-      qf[s] = fr < G ? *reinterpret_cast<const bf16x8*>(s_q + fr * D + 32 * s + 8 * fh)
+      qf[s] = fr < G ? *reinterpret_cast<const bf16x8*>(s_q + fr * D + (F8 ? f8_qoff(s, fh) : 32 * s + 8 * fh))
                      : (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
   } else {
     const int g = fr < G ? fr : 0;
     const bf16_t* qp = a.q + (size_t)b * a.q_stride + (kvh * G + g) * D + 8 * fh;
 #pragma unroll
     for (int s = 0; s < C::KS; ++s) {
-      const bf16x8 v = *reinterpret_cast<const bf16x8*>(qp + 32 * s);
+      const bf16x8 v = *reinterpret_cast<const bf16x8*>(F8 ? qp - 8 * fh + f8_qoff(s, fh) : qp + 32 * s);
       qf[s] = fr < G ? v : (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
     }
   }
@@ -1072,7 +1184,48 @@ __device__ __forceinline__ void attn_decode_block(const DecodeArgs& a, int part,
 
   for (int kt = kt0 + wid_u; kt < kt1; kt += NW) {
     bf16x8 kf[4][C::KS];
-    if constexpr (KL) {
+    u32x4 f8_v[F8 ? 8 : 1];  // F8: the wave's V tile, 16-byte chunk 64 i + lane in f8_v[i]
+    f32x4 ksc[4], vsc[4];    // F8: row scales of this lane's keys 16 t + 4 fh + [0, 4)
+    if constexpr (F8) {
+      const size_t blk = (size_t)bt[kt] * a.Hkv + kvh;
+      const unsigned char* kb = reinterpret_cast<const unsigned char*>(a.kc) + blk * F8_TILEB;
+      const unsigned char* vb = reinterpret_cast<const unsigned char*>(a.vc) + blk * F8_TILEB;
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // previous tile's K / V reads retired
+      if constexpr (KL)
+        stage_kv<64, false, NT, 1>(sK, 0, 1, lane,
+                                   [&](int r) { return reinterpret_cast<const bf16_t*>(kb + (size_t)r * F8_D); });
+      u32x4 kraw[4][2];
+      if constexpr (!KL) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) kraw[t][j] = f8_ld16<NT>(kb + (16 * t + fr) * F8_D + 16 * (4 * j + fh));
+      }
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        ksc[t] = *reinterpret_cast<const f32x4*>(a.ks + blk * KT + 16 * t + 4 * fh);
+        vsc[t] = *reinterpret_cast<const f32x4*>(a.vs + blk * KT + 16 * t + 4 * fh);
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) f8_v[i] = f8_ld16<NT>(vb + 16 * (64 * i + lane));
+      if constexpr (KL) {
+        // every load above has landed (the K tile's LDS-DMA among them); the builtin keeps the compiler's
+        // own counter model in step
+        __builtin_amdgcn_s_waitcnt((0x7 << 4) | (0xF << 8));
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) f8_load_k(sK, t, j, lane, kf[t][2 * j], kf[t][2 * j + 1]);
+      } else {
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            kf[t][2 * j] = kv8_to_bf16(kraw[t][j][0], kraw[t][j][1]);
+            kf[t][2 * j + 1] = kv8_to_bf16(kraw[t][j][2], kraw[t][j][3]);
+          }
+      }
+    } else if constexpr (KL) {
       if (!(pre && kt == kt0 + wid_u)) {  // else staged before the prologue
         const size_t base = ((size_t)bt[kt] * a.Hkv + kvh) * KT * D;
         const bf16_t* kb = a.kc + base;
@@ -1144,7 +1297,7 @@ __device__ __forceinline__ void attn_decode_block(const DecodeArgs& a, int part,
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int kj = k0 + 16 * t + 4 * fh + r;
-        const float x = kj < kv_len ? s4[t][r] * a.scale_log2 : -INFINITY;
+        const float x = kj < kv_len ? (F8 ? s4[t][r] * ksc[t][r] : s4[t][r]) * a.scale_log2 : -INFINITY;
         s4[t][r] = x;
         mx = fmaxf(mx, x);
       }
@@ -1161,8 +1314,11 @@ __device__ __forceinline__ void attn_decode_block(const DecodeArgs& a, int part,
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const float p = __builtin_amdgcn_exp2f(s4[t][r] - m_use);
-        s4[t][r] = p;
         ls += p;
+        if constexpr (F8)  // the row sum takes the unscaled p; slots past kv_len may hold any scale bits
+          s4[t][r] = k0 + 16 * t + 4 * fh + r < kv_len ? p * vsc[t][r] : 0.f;
+        else
+          s4[t][r] = p;
       }
     l_i = l_i * alpha + ls;
     m_i = m_new;
@@ -1170,7 +1326,11 @@ __device__ __forceinline__ void attn_decode_block(const DecodeArgs& a, int part,
     for (int dt = 0; dt < C::DT; ++dt) o[dt] *= alpha;
     const bf16x8 pb0 = pack_p(s4[0], s4[1]);
     const bf16x8 pb1 = pack_p(s4[2], s4[3]);
-    if constexpr (KL)
+    if constexpr (F8) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) f8_v_to_lds(sV, 64 * i + lane, f8_v[i]);
+      asm volatile("" ::: "memory");  // the wave's own LDS writes stay ahead of its transposed reads (LDS is in order)
+    } else if constexpr (KL)
       __builtin_amdgcn_s_waitcnt((0x7 << 4) | (0xF << 8));  // V tile landed (vmcnt(0), seen by the compiler)
     else
       wait_vmcnt0();  // V tile landed in this wave's LDS
@@ -1225,10 +1385,10 @@ __device__ __forceinline__ void attn_decode_block(const DecodeArgs& a, int part,
   }
 }
 
-template <int D, int G, bool NT = false, int NW = 4, int DG = 0, bool KL = false>
+template <int D, int G, bool NT = false, int NW = 4, int DG = 0, bool KL = false, bool F8 = false>
 __global__ __launch_bounds__(NW * 64, (NW == 4 && !KL) ? 2 : 1) void attn_decode_kernel(DecodeArgs a) {
-  __shared__ __attribute__((aligned(16))) char smem[decode_lds_bytes<D, G, NW, KL>()];
-  attn_decode_block<D, G, NT, NW, DG, KL>(a, blockIdx.x, blockIdx.y, blockIdx.z, smem);
+  __shared__ __attribute__((aligned(16))) char smem[decode_lds_bytes<D, G, NW, KL, F8>()];
+  attn_decode_block<D, G, NT, NW, DG, KL, F8>(a, blockIdx.x, blockIdx.y, blockIdx.z, smem);
 }
 
 // merge split-K partitions: grid (Hq, B), block D threads. The partition statistics are loaded by
@@ -1321,6 +1481,21 @@ hipError_t launch_prefill(PrefillArgs a, int n_tiles, hipStream_t st) {
     hipLaunchKernelGGL((attn_prefill_kernel<D, GB, CAUSAL, PAGED, false, 8>), grid, dim3(512), 0, st, a);
   else
     hipLaunchKernelGGL((attn_prefill_kernel<D, GB, CAUSAL, PAGED>), grid, dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// fp8 cache: the generic kernel (causal, paged, D 128) with the block shapes of launch_prefill, so the host's
+// tile list (ragk_attn_prefill_qtile) is the same for both cache formats.
+template <int GB>
+hipError_t launch_prefill_fp8(PrefillArgs a, int n_tiles, hipStream_t st) {
+  const int G = a.Hq / a.Hkv;
+  const int n_hg = a.Hkv * (G / GB);
+  a.n_hg = n_hg;
+  const dim3 grid(n_tiles * n_hg);
+  if constexpr (GB == 4)
+    hipLaunchKernelGGL((attn_prefill_kernel<128, GB, true, true, false, 8, 0, false, true>), grid, dim3(512), 0, st, a);
+  else
+    hipLaunchKernelGGL((attn_prefill_kernel<128, GB, true, true, false, 4, 0, false, true>), grid, dim3(256), 0, st, a);
   return hipGetLastError();
 }
 
@@ -1431,9 +1606,42 @@ RAGK_API int ragk_attn_decode_rope(const float* P, int S, int ldp, const int* po
   return launch_attn_decode(a, B, D, max_parts, st);
 }
 
+// fp8 cache (a.ks set): the same routes as the bf16 D = 128 dispatch below -- the single-partition grid on
+// KL-style 4-wave blocks (K tiles by LDS-DMA), else split-K 4-wave blocks + reduce; nt loads on and off.
+static int launch_attn_decode_fp8(DecodeArgs a, int B, int D, int max_parts, hipStream_t st) {
+  const int Hq = a.Hq, Hkv = a.Hkv;
+  const int G = Hq / Hkv;
+  if (D != 128 || !a.vs) return (int)hipErrorInvalidValue;
+  dim3 grid(max_parts, Hkv, B);
+  if (G == 4 && max_parts == 1 && g_decode_kl && g_decode_nw8_min > 0 && B * Hkv >= g_decode_nw8_min) {
+    if (g_decode_nt)
+      hipLaunchKernelGGL((attn_decode_kernel<128, 4, true, 4, 0, true, true>), grid, dim3(256), 0, st, a);
+    else
+      hipLaunchKernelGGL((attn_decode_kernel<128, 4, false, 4, 0, true, true>), grid, dim3(256), 0, st, a);
+    return (int)hipGetLastError();
+  }
+#define RAGK_DC8(GG)                                                                               \
+  if (G == GG) {                                                                                   \
+    if (g_decode_nt)                                                                               \
+      hipLaunchKernelGGL((attn_decode_kernel<128, GG, true, 4, 0, false, true>), grid, dim3(256), 0, st, a);  \
+    else                                                                                           \
+      hipLaunchKernelGGL((attn_decode_kernel<128, GG, false, 4, 0, false, true>), grid, dim3(256), 0, st, a); \
+    if (max_parts > 1 && !g_decode_defer)                                                          \
+      hipLaunchKernelGGL(attn_decode_reduce_kernel, dim3(Hq, B), dim3(128), 0, st, a, 128);        \
+    return (int)hipGetLastError();                                                                 \
+  }
+  RAGK_DC8(4)
+  RAGK_DC8(8)
+  RAGK_DC8(1)
+  RAGK_DC8(2)
+#undef RAGK_DC8
+  return (int)hipErrorInvalidValue;
+}
+
 static int launch_attn_decode(DecodeArgs a, int B, int D, int max_parts, hipStream_t st) {
   const int Hq = a.Hq, Hkv = a.Hkv;
   const int G = Hq / Hkv;
+  if (a.ks) return launch_attn_decode_fp8(a, B, D, max_parts, st);
   dim3 grid(max_parts, Hkv, B);
   if (D == 128 && G == 4 && max_parts == 1 && g_decode_nw8_min > 0 && B * Hkv >= g_decode_nw8_min) {
     // one partition per sequence over >= 1 block per CU: 8-wave blocks, no merge launch
@@ -1469,3 +1677,48 @@ static int launch_attn_decode(DecodeArgs a, int B, int D, int max_parts, hipStre
   return (int)hipErrorInvalidValue;
 }
 
+
+// ---- fp8 KV cache entry points (kv_fp8.h): k8 / v8 [nblocks][Hkv][64][128] e4m3 bytes, ks / vs [nblocks][Hkv][64]
+// fp32 row scales. Same arguments as the bf16 forms plus the two scale arrays; D must be 128.
+RAGK_API int ragk_attn_prefill_fp8(const void* q, int q_stride, const void* k8, const void* v8, const float* ks,
+                                   const float* vs, const int* block_tables, int bt_stride, const int* cu_q,
+                                   const int* kv_lens, const int* tiles, int n_tiles, void* out, int out_stride,
+                                   int Hq, int Hkv, int D, float scale, hipStream_t st) {
+  if (n_tiles <= 0) return 0;
+  if (Hq % Hkv || D != 128 || !k8 || !v8 || !ks || !vs || !block_tables) return (int)hipErrorInvalidValue;
+  PrefillArgs a{(const bf16_t*)q, q_stride, (const bf16_t*)k8, (const bf16_t*)v8, 0, block_tables, bt_stride,
+                cu_q, nullptr, kv_lens, tiles, (bf16_t*)out, out_stride, Hq, Hkv, scale * 1.4426950408889634f,
+                0u, 0, ks, vs};
+  const int G = Hq / Hkv;
+  if (G % 4 == 0) return (int)launch_prefill_fp8<4>(a, n_tiles, st);
+  if (G % 2 == 0) return (int)launch_prefill_fp8<2>(a, n_tiles, st);
+  return (int)launch_prefill_fp8<1>(a, n_tiles, st);
+}
+
+RAGK_API int ragk_attn_decode_fp8(const void* q, int q_stride, const void* k8, const void* v8, const float* ks,
+                                  const float* vs, const int* block_tables, int bt_stride, const int* kv_lens,
+                                  float* part_o, float* part_ml, void* out, int out_stride, int B, int Hq, int Hkv,
+                                  int D, int part_tiles, int max_parts, float scale, hipStream_t st) {
+  if (B <= 0) return 0;
+  if (Hq % Hkv || part_tiles < 1 || max_parts < 1 || max_parts > RED_MAXP || !ks || !vs)
+    return (int)hipErrorInvalidValue;
+  DecodeArgs a{(const bf16_t*)q, q_stride, (const bf16_t*)k8, (const bf16_t*)v8, block_tables, bt_stride, kv_lens,
+               part_o, part_ml, (bf16_t*)out, out_stride, Hq, Hkv, part_tiles, max_parts,
+               scale * 1.4426950408889634f, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, ks, vs};
+  return launch_attn_decode(a, B, D, max_parts, st);
+}
+
+RAGK_API int ragk_attn_decode_rope_fp8(const float* P, int S, int ldp, const int* positions, const int* slots,
+                                       const float* cos_t, const float* sin_t, void* k8, void* v8, float* ks,
+                                       float* vs, const int* block_tables, int bt_stride, const int* kv_lens,
+                                       float* part_o, float* part_ml, void* out, int out_stride, int B, int Hq,
+                                       int Hkv, int D, int part_tiles, int max_parts, float scale, hipStream_t st) {
+  if (B <= 0) return 0;
+  if (Hq % Hkv || part_tiles < 1 || max_parts < 1 || max_parts > RED_MAXP || S < 1 || D != 128 ||
+      ldp < (Hq + 2 * Hkv) * D || !P || !positions || !slots || !cos_t || !sin_t || !ks || !vs)
+    return (int)hipErrorInvalidValue;
+  DecodeArgs a{nullptr, 0, (const bf16_t*)k8, (const bf16_t*)v8, block_tables, bt_stride, kv_lens,
+               part_o, part_ml, (bf16_t*)out, out_stride, Hq, Hkv, part_tiles, max_parts,
+               scale * 1.4426950408889634f, P, (long long)B * ldp, ldp, S, positions, slots, cos_t, sin_t, ks, vs};
+  return launch_attn_decode(a, B, D, max_parts, st);
+}

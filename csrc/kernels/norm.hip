@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "kv_fp8.h"
 using namespace ragk;
 
 namespace {
@@ -452,6 +453,94 @@ __global__ __launch_bounds__(NT) void rope_kv_partials_kernel(const float* __res
   }
 }
 
+// fp8-cache forms of rope_kv_kernel / rope_kv_partials_kernel (D = 128, RoPE always applied): the same bf16
+// q / k / v values, but a k or v row goes to the cache as 128 e4m3 bytes + one fp32 scale (kv_fp8.h:
+// bit-identical to quantize_rows of the bf16 cache row). One (head, v) item per thread holds the row's
+// d = 8v + [0, 8) and d = 64 + 8v + [0, 8); the 8 consecutive threads of a head reduce the row's amax
+// across lanes. Row `slot` of KV head kh: data at row index ((slot / BS) * Hkv + kh) * BS + slot % BS.
+__device__ __forceinline__ size_t kv8_row(int slot, int kh, int Hkv, int BS) {
+  return ((size_t)(slot / BS) * Hkv + kh) * BS + (slot % BS);
+}
+
+__global__ __launch_bounds__(NT) void rope_kv_fp8_kernel(bf16_t* qkv, int ld, const int* __restrict__ positions,
+                                                         const float* __restrict__ cos_t,
+                                                         const float* __restrict__ sin_t,
+                                                         const int* __restrict__ slots, unsigned char* k8,
+                                                         unsigned char* v8, float* ks, float* vs, int Hq, int Hkv,
+                                                         int BS) {
+  constexpr int D = 128, half = 64, vpr = 8;
+  const int t = blockIdx.x;
+  const int pos = positions[t];
+  const int slot = slots ? slots[t] : -1;
+  bf16_t* row = qkv + (size_t)t * ld;
+  const float* ct = cos_t + (size_t)pos * half;
+  const float* st = sin_t + (size_t)pos * half;
+  const int nh = Hq + 2 * Hkv;
+  for (int i = threadIdx.x; i < nh * vpr; i += NT) {  // whole 8-lane groups enter together
+    const int h = i / vpr, v = i % vpr;
+    bf16_t* hp = row + h * D;
+    float x1[8], x2[8], o1[8], o2[8];
+    unpack8(*reinterpret_cast<const u32x4*>(hp + v * 8), x1);
+    unpack8(*reinterpret_cast<const u32x4*>(hp + half + v * 8), x2);
+    if (h >= Hq + Hkv) {  // v head: unrotated
+      if (slot >= 0) {
+        const size_t r = kv8_row(slot, h - Hq - Hkv, Hkv, BS);
+        kv8_store_row128(x1, x2, v, v8 + r * D, vs + r);
+      }
+      continue;
+    }
+    rope8(x1, x2, ct + v * 8, st + v * 8, o1, o2);
+    *reinterpret_cast<u32x4*>(hp + v * 8) = pack8(o1);
+    *reinterpret_cast<u32x4*>(hp + half + v * 8) = pack8(o2);
+    if (h >= Hq && slot >= 0) {
+      const size_t r = kv8_row(slot, h - Hq, Hkv, BS);
+      kv8_store_row128(o1, o2, v, k8 + r * D, ks + r);
+    }
+  }
+}
+
+__global__ __launch_bounds__(NT) void rope_kv_partials_fp8_kernel(const float* __restrict__ P, int S, int T, int ldp,
+                                                                  bf16_t* q_out, int ldq,
+                                                                  const int* __restrict__ positions,
+                                                                  const float* __restrict__ cos_t,
+                                                                  const float* __restrict__ sin_t,
+                                                                  const int* __restrict__ slots, unsigned char* k8,
+                                                                  unsigned char* v8, float* ks, float* vs, int Hq,
+                                                                  int Hkv, int BS) {
+  constexpr int D = 128, half = 64, vpr = 8;
+  const int t = blockIdx.x, hg = blockIdx.y, ngroups = gridDim.y;
+  const int pos = positions[t];
+  const int slot = slots[t];
+  const size_t slab = (size_t)T * ldp;
+  const float* prow = P + (size_t)t * ldp;
+  const float* ct = cos_t + (size_t)pos * half;
+  const float* st = sin_t + (size_t)pos * half;
+  const int nh = Hq + 2 * Hkv;
+  for (int i = threadIdx.x + hg * NT; i < nh * vpr; i += NT * ngroups) {
+    const int hd = i / vpr, v = i % vpr;
+    float x1[8], x2[8];
+    sum_partials8(prow + hd * D + v * 8, S, slab, x1);
+    sum_partials8(prow + hd * D + half + v * 8, S, slab, x2);
+    if (hd >= Hq + Hkv) {
+      if (slot >= 0) {
+        const size_t r = kv8_row(slot, hd - Hq - Hkv, Hkv, BS);
+        kv8_store_row128(x1, x2, v, v8 + r * D, vs + r);
+      }
+      continue;
+    }
+    float o1[8], o2[8];
+    rope8(x1, x2, ct + v * 8, st + v * 8, o1, o2);
+    if (hd < Hq) {
+      bf16_t* qp = q_out + (size_t)t * ldq + hd * D;
+      *reinterpret_cast<u32x4*>(qp + v * 8) = pack8(o1);
+      *reinterpret_cast<u32x4*>(qp + half + v * 8) = pack8(o2);
+    } else if (slot >= 0) {
+      const size_t r = kv8_row(slot, hd - Hq, Hkv, BS);
+      kv8_store_row128(o1, o2, v, k8 + r * D, ks + r);
+    }
+  }
+}
+
 }  // namespace
 
 RAGK_API int ragk_rmsnorm(const void* x, int ldx, void* resid, int ldr, const void* w, void* out, int ldo, int rows,
@@ -557,5 +646,32 @@ RAGK_API int ragk_rope_kv_partials(const float* P, int S, int T, int ldp, void* 
   const int groups = std::max(1, std::min((items + 63) / 64, std::max(4, (512 + T - 1) / T)));
   hipLaunchKernelGGL(rope_kv_partials_kernel, dim3(T, groups), dim3(NT), 0, st, P, S, T, ldp, (bf16_t*)q_out,
                      ldq, positions, cos_t, sin_t, slots, (bf16_t*)kc, (bf16_t*)vc, Hq, Hkv, D, BS);
+  return (int)hipGetLastError();
+}
+
+// fp8 KV cache (kv_fp8.h): k8 / v8 [nblocks][Hkv][BS][128] e4m3 bytes, ks / vs [nblocks][Hkv][BS] fp32 row scales.
+RAGK_API int ragk_rope_kv_fp8(void* qkv, int ld, const int* positions, const float* cos_t, const float* sin_t,
+                              const int* slots, void* k8, void* v8, float* ks, float* vs, int T, int Hq, int Hkv,
+                              int D, int BS, hipStream_t st) {
+  if (T <= 0) return 0;
+  if (D != 128 || !positions || !cos_t || !sin_t || (slots && (!k8 || !v8 || !ks || !vs)))
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(rope_kv_fp8_kernel, dim3(T), dim3(NT), 0, st, (bf16_t*)qkv, ld, positions, cos_t, sin_t, slots,
+                     (unsigned char*)k8, (unsigned char*)v8, ks, vs, Hq, Hkv, BS);
+  return (int)hipGetLastError();
+}
+
+RAGK_API int ragk_rope_kv_partials_fp8(const float* P, int S, int T, int ldp, void* q_out, int ldq,
+                                       const int* positions, const float* cos_t, const float* sin_t,
+                                       const int* slots, void* k8, void* v8, float* ks, float* vs, int Hq, int Hkv,
+                                       int D, int BS, hipStream_t st) {
+  if (T <= 0) return 0;
+  if (D != 128 || S < 1 || !positions || !cos_t || !sin_t || !slots || !k8 || !v8 || !ks || !vs)
+    return (int)hipErrorInvalidValue;
+  const int items = (Hq + 2 * Hkv) * (D / 16);
+  const int groups = std::max(1, std::min((items + 63) / 64, std::max(4, (512 + T - 1) / T)));
+  hipLaunchKernelGGL(rope_kv_partials_fp8_kernel, dim3(T, groups), dim3(NT), 0, st, P, S, T, ldp, (bf16_t*)q_out,
+                     ldq, positions, cos_t, sin_t, slots, (unsigned char*)k8, (unsigned char*)v8, ks, vs, Hq, Hkv,
+                     BS);
   return (int)hipGetLastError();
 }

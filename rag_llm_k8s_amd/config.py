@@ -60,6 +60,7 @@ class RagConfig:
     mixed_prefill_tokens: int = 0
     kv_cache_fraction: float = 0.80  # of free HBM after weights
     kv_cache_blocks: int = 0  # explicit override (64-token blocks)
+    kv_cache_dtype: str = "bf16"  # bf16 | fp8 (e4m3 K / V + one fp32 scale per cached row; head_dim 128 models)
     embed_batch_tokens: int = 65536
     max_embed_len: int = 8192
     use_cuda_graphs: bool = True
@@ -92,7 +93,7 @@ class RagConfig:
             "TRUNCATE_PROMPT": ("truncate_prompt", str), "REQUEST_TIMEOUT_S": ("request_timeout_s", float),
             "STEP_TIMEOUT_S": ("step_timeout_s", float), "WATCHDOG_EXIT": ("watchdog_exit", bool),
             "INDEX_RECOVERY": ("index_recovery", str), "IGNORE_EOS": ("ignore_eos", bool),
-            "INDEX_SHARDED": ("index_sharded", bool),
+            "INDEX_SHARDED": ("index_sharded", bool), "KV_CACHE_DTYPE": ("kv_cache_dtype", str),
         }
         for env, (attr, cast) in m.items():
             setattr(c, attr, _env(env, getattr(c, attr), cast))
@@ -103,6 +104,9 @@ class RagConfig:
             if not hasattr(c, k):
                 raise AttributeError("unknown config key %s" % k)
             setattr(c, k, v)
+        c.kv_cache_dtype = str(c.kv_cache_dtype).strip().lower()
+        if c.kv_cache_dtype not in ("bf16", "fp8"):
+            raise ValueError("KV_CACHE_DTYPE must be bf16 or fp8, got %r" % c.kv_cache_dtype)
         return c
 
     def resolved_device(self) -> str:

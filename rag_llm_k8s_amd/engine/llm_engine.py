@@ -33,6 +33,7 @@ import torch
 
 from ..models.llama import StepInput
 from ..ops.backend import AttnMeta
+from ..ops.fp8 import kv_cache_dtype_name, kv_cache_torch_dtype
 from ..utils import faults
 from .kv_manager import BLOCK, make_block_manager
 
@@ -96,7 +97,7 @@ class Sequence:
 class LLMEngine:
     def __init__(self, model, num_blocks: int, max_batch: int = 64, max_prefill_tokens: int = 32768,
                  max_model_len: int = 16384, eos_ids=(), use_graphs: bool = True, tp_group=None, top_k_cap: int = 64,
-                 graph_buckets=None, mixed_prefill_tokens: int = 0):
+                 graph_buckets=None, mixed_prefill_tokens: int = 0, kv_dtype="bf16"):
         self.model = model
         self.device = model.device
         self.max_batch = max_batch
@@ -110,7 +111,13 @@ class LLMEngine:
         self.eos = set(int(e) for e in eos_ids)
         self.bm = make_block_manager(num_blocks)
         self.max_blocks = -(-max_model_len // BLOCK)
-        model.allocate_kv_cache(num_blocks)
+        # "bf16" (default) or "fp8": e4m3 K / V with one fp32 scale per cached row (ops/fp8.Fp8KV); a model the
+        # fp8 kernels do not cover (head_dim != 128, GPT-2) raises here instead of silently running bf16
+        self.kv_dtype = kv_cache_dtype_name(kv_dtype)
+        if self.kv_dtype == "bf16":
+            model.allocate_kv_cache(num_blocks)
+        else:
+            model.allocate_kv_cache(num_blocks, kv_cache_torch_dtype(kv_dtype))
         self.waiting = deque()
         self.running: List[Sequence] = []
         self.lock = threading.Lock()
@@ -135,7 +142,7 @@ class LLMEngine:
         # RAGK_DECODE_TIMING=1: (start, end) CUDA events around every async decode graph replay
         self._timing = [] if os.environ.get("RAGK_DECODE_TIMING") == "1" else None
         self.stats = dict(prefill_steps=0, decode_steps=0, prefill_tokens=0, decode_tokens=0, prefill_s=0.0,
-                          decode_s=0.0)
+                          decode_s=0.0, kv_dtype=self.kv_dtype)
         # two pinned staging buffers, alternated per step: with the asynchronous decode pipeline a
         # step's H2D copy may still be pending while the host stages the next one
         self._pins = [torch.empty(1 << 20 if self.is_cuda else 0, dtype=torch.int32, pin_memory=self.is_cuda)

@@ -108,12 +108,17 @@ class GPT2Model:
         self.kv_cache = None
 
     def allocate_kv_cache(self, num_blocks, dtype=torch.bfloat16):
+        if dtype != torch.bfloat16:  # the fp8 KV cache kernels cover head_dim 128 RoPE models only
+            raise ValueError("GPT-2 serves a bf16 KV cache only (kv_cache_dtype=%s is not supported: the fp8 cache "
+                             "needs head_dim 128 and RoPE)" % (dtype,))
         self.kv_cache = [(torch.zeros(num_blocks, self.Hkv, 64, self.D, dtype=dtype, device=self.device),
                           torch.zeros(num_blocks, self.Hkv, 64, self.D, dtype=dtype, device=self.device))
                          for _ in range(self.cfg.n_layer)]
         return self.kv_cache
 
-    def kv_bytes_per_block(self):
+    def kv_bytes_per_block(self, dtype=torch.bfloat16):
+        if dtype != torch.bfloat16:
+            raise ValueError("GPT-2 serves a bf16 KV cache only (kv_cache_dtype=%s is not supported)" % (dtype,))
         return 2 * self.cfg.n_layer * self.Hkv * 64 * self.D * 2
 
     def hidden_states(self, inp):

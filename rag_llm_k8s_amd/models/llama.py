@@ -23,6 +23,7 @@ from typing import List, Optional
 import torch
 
 from ..ops.backend import AttnMeta, get_backend
+from ..ops.fp8 import FP8, alloc_fp8_kv, check_fp8_kv_head_dim, kv_cache_torch_dtype
 from ..ops.reference import pack_gate_up, rope_tables
 
 # decode batches up to this size run the down projection on the register-streaming GEMM (fused residual)
@@ -254,12 +255,24 @@ class LlamaModel:
         self.sp_min_tokens = int(os.environ.get("RAGK_SP_MIN_TOKENS", "256"))
 
     def allocate_kv_cache(self, num_blocks, dtype=torch.bfloat16):
+        """Per layer a (k, v) pair: bf16 tensors [nblocks, Hkv, 64, D], or for dtype float8_e4m3fn a pair of
+        ops/fp8.Fp8KV (e4m3 data + one fp32 scale per cached row; head_dim 128 only)."""
+        dtype = kv_cache_torch_dtype(dtype)
+        if dtype == FP8:
+            check_fp8_kv_head_dim(self.D)
+            self.kv_cache = [(alloc_fp8_kv(num_blocks, self.Hkv, 64, self.D, self.device),
+                              alloc_fp8_kv(num_blocks, self.Hkv, 64, self.D, self.device))
+                             for _ in range(self.cfg.num_hidden_layers)]
+            return self.kv_cache
         self.kv_cache = [(torch.zeros(num_blocks, self.Hkv, 64, self.D, dtype=dtype, device=self.device),
                           torch.zeros(num_blocks, self.Hkv, 64, self.D, dtype=dtype, device=self.device))
                          for _ in range(self.cfg.num_hidden_layers)]
         return self.kv_cache
 
     def kv_bytes_per_block(self, dtype=torch.bfloat16):
+        dtype = kv_cache_torch_dtype(dtype)
+        if dtype == FP8:  # one byte per element + one fp32 scale per (token, KV head) row
+            return 2 * self.cfg.num_hidden_layers * self.Hkv * 64 * (self.D + 4)
         return 2 * self.cfg.num_hidden_layers * self.Hkv * 64 * self.D * torch.tensor([], dtype=dtype).element_size()
 
     def _allreduce(self, x):

@@ -72,6 +72,12 @@ _SIGS = {
     "ragk_attn_prefill": [P, I, P, P, I, P, I, P, P, P, P, I, P, I, I, I, I, I, I, F, S],
     "ragk_attn_decode": [P, I, P, P, P, I, P, P, P, P, I, I, I, I, I, I, I, F, S],
     "ragk_attn_decode_rope": [P, I, I, P, P, P, P, P, P, P, I, P, P, P, P, I, I, I, I, I, I, I, F, S],
+    # fp8 KV cache forms (kv_fp8.h): the bf16 signatures plus the k / v row-scale arrays
+    "ragk_rope_kv_fp8": [P, I, P, P, P, P, P, P, P, P, I, I, I, I, I, S],
+    "ragk_rope_kv_partials_fp8": [P, I, I, I, P, I, P, P, P, P, P, P, P, P, I, I, I, I, S],
+    "ragk_attn_prefill_fp8": [P, I, P, P, P, P, P, I, P, P, P, I, P, I, I, I, I, F, S],
+    "ragk_attn_decode_fp8": [P, I, P, P, P, P, P, I, P, P, P, P, I, I, I, I, I, I, I, F, S],
+    "ragk_attn_decode_rope_fp8": [P, I, I, P, P, P, P, P, P, P, P, P, I, P, P, P, P, I, I, I, I, I, I, I, F, S],
     "ragk_topk_candidates": [P, I, I, I, I, I, I, P, P, S],
     "ragk_sample_candidates": [P, P, I, I, P, P, P, P, P, P, P, S],
     "ragk_sample_candidates_lists": [P, P, I, I, I, P, P, P, P, P, P, P, S],

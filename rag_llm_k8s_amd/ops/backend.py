@@ -18,7 +18,7 @@ from typing import List, Optional
 import torch
 
 from . import reference as R
-from .fp8 import Fp8Weight, reference_linear
+from .fp8 import Fp8KV, Fp8Weight, reference_linear
 
 KV_BLOCK = 64
 
@@ -108,8 +108,11 @@ class TorchBackend:
             s = slots.long()
             ok = s >= 0
             s = s[ok]
-            kc[s // KV_BLOCK, :, s % KV_BLOCK] = k[ok]
-            vc[s // KV_BLOCK, :, s % KV_BLOCK] = v[ok]
+            for cache, rows in ((kc, k[ok]), (vc, v[ok])):
+                if isinstance(cache, Fp8KV):  # fp8 cache: quantize_rows of the bf16 row the bf16 cache would hold
+                    cache.write_rows(s // KV_BLOCK, s % KV_BLOCK, rows)
+                else:
+                    cache[s // KV_BLOCK, :, s % KV_BLOCK] = rows
 
     def gemm_rope_kv(self, x, w, positions, cos_t, sin_t, slots, kc, vc, Hq, Hkv, D):
         """qkv projection + rope_kv (the GPU backend fuses them into the GEMM epilogue)."""
@@ -177,9 +180,15 @@ class TorchBackend:
         qq = q[:, :Hq * D].reshape(T, Hq, D)
         bt = meta.block_tables.cpu()
         lens = meta.host_kv_lens
+
+        def view(cache, s):
+            if isinstance(cache, Fp8KV):  # data.float() * scale[..., None] over the sequence's blocks
+                return (R.paged_kv_view(cache.data.view(torch.uint8), bt[s], lens[s], KV_BLOCK).view(cache.data.dtype).float()
+                        * _paged_scale_view(cache.scale, bt[s], lens[s])[..., None])
+            return R.paged_kv_view(cache, bt[s], lens[s], KV_BLOCK)
+
         o = R.attention_varlen(qq, None, None, meta.cu_q.cpu(), lens, True, 1.0 / math.sqrt(D),
-                               k_full=lambda s: R.paged_kv_view(kc, bt[s], lens[s], KV_BLOCK),
-                               v_full=lambda s: R.paged_kv_view(vc, bt[s], lens[s], KV_BLOCK))
+                               k_full=lambda s: view(kc, s), v_full=lambda s: view(vc, s))
         out.copy_(o.reshape(T, Hq * D))
         return out
 
@@ -366,6 +375,12 @@ class NativeBackend(TorchBackend):
 
     def sample_candidates(self, cand_v, cand_i, temps, top_ks, top_ps, seeds, steps, list_len=None):
         return self.n.sample_candidates(cand_v, cand_i, temps, top_ks, top_ps, seeds, steps, list_len=list_len)
+
+
+def _paged_scale_view(scale, block_table, L):
+    """[L, Hkv] row scales of one sequence from an fp8 cache's scale array [nblocks, Hkv, 64]."""
+    nb = (L + KV_BLOCK - 1) // KV_BLOCK
+    return scale[block_table[:nb].long()].permute(0, 2, 1).reshape(nb * KV_BLOCK, scale.shape[1])[:L]
 
 
 def _lens_dev(cu):

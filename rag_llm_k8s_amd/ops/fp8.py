@@ -9,6 +9,9 @@ gate/up layout and fused qkv rows carry over unchanged. On the GPU:
                       with the block-scaled fp8 MFMA (gemm_fp8_tile).
 `reference_linear` reproduces exactly that arithmetic in fp32 (the oracle of the GPU tests and
 the CPU path).
+
+The opt-in fp8 KV cache (`Fp8KV`, KV_CACHE_DTYPE=fp8) reuses the activation quantization: a cached k / v row is
+`quantize_rows` of the bf16 row, on every write path of both backends (csrc/kernels/kv_fp8.h on the GPU).
 """
 from __future__ import annotations
 
@@ -41,6 +44,68 @@ class Fp8Weight:
 
     def nbytes(self):
         return self.w8.numel() + 4 * self.scale.numel()
+
+
+@dataclass
+class Fp8KV:
+    """One side (K or V) of an fp8 paged KV cache: `data` [nblocks, Hkv, 64, D] e4m3fn and one fp32 `scale` per
+    cached row [nblocks, Hkv, 64]; a row x is stored as quantize_rows(x), x ~= data * scale[..., None]. Every
+    writer (GPU or CPU) produces exactly quantize_rows of the bf16 value the bf16 cache would hold."""
+    data: torch.Tensor
+    scale: torch.Tensor
+
+    @property
+    def shape(self):
+        return self.data.shape
+
+    @property
+    def device(self):
+        return self.data.device
+
+    @property
+    def dtype(self):
+        return self.data.dtype
+
+    def dequant(self, dtype=torch.float32):
+        return (self.data.float() * self.scale[..., None]).to(dtype)
+
+    def nbytes(self):
+        return self.data.numel() + 4 * self.scale.numel()
+
+    def write_rows(self, blocks, offs, rows):
+        """rows [n, Hkv, D] (bf16 values) -> cache rows (blocks[i], :, offs[i]), quantized per (token, head)."""
+        n, Hkv, D = rows.shape
+        q, s = quantize_rows(rows.reshape(n * Hkv, D))
+        self.data.view(torch.uint8)[blocks, :, offs] = q.view(torch.uint8).view(n, Hkv, D)  # bytes: no fp8 index_put
+        self.scale[blocks, :, offs] = s.view(n, Hkv)
+
+
+def alloc_fp8_kv(num_blocks, Hkv, block, D, device):
+    return Fp8KV(torch.zeros((num_blocks, Hkv, block, D), dtype=torch.uint8, device=device).view(FP8),
+                 torch.ones((num_blocks, Hkv, block), dtype=torch.float32, device=device))
+
+
+KV_CACHE_DTYPES = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "fp8": FP8, "fp8_e4m3": FP8}
+
+
+def kv_cache_torch_dtype(dtype):
+    """"bf16" | "fp8" (or a torch dtype) -> the KV cache's torch dtype; anything else is an error."""
+    if isinstance(dtype, torch.dtype):
+        return dtype
+    try:
+        return KV_CACHE_DTYPES[str(dtype).strip().lower()]
+    except KeyError:
+        raise ValueError("kv cache dtype must be 'bf16' or 'fp8', got %r" % (dtype,)) from None
+
+
+def kv_cache_dtype_name(dtype):
+    return "fp8" if kv_cache_torch_dtype(dtype) == FP8 else "bf16"
+
+
+def check_fp8_kv_head_dim(D, what="this model"):
+    """The fp8 KV cache kernels are built for head_dim 128 only: refuse instead of falling back to bf16."""
+    if D != 128:
+        raise ValueError("fp8 KV cache needs head_dim 128; %s has head_dim %d (use kv_cache_dtype=bf16)" % (what, D))
 
 
 def quantize_weight(w: torch.Tensor) -> Fp8Weight:

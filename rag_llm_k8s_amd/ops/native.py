@@ -14,12 +14,28 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
+from .fp8 import FP8, Fp8KV
 from .reference import EPI
 
 
 def _req(cond, msg):
     if not cond:
         raise ValueError(msg)
+
+
+def _kv8(k_cache, v_cache, Hkv, D, dev):
+    """Host-side checks of an fp8 KV cache pair (ops/fp8.Fp8KV): e4m3 data [nb, Hkv, 64, 128] and fp32 row
+    scales [nb, Hkv, 64], contiguous, on the launch device. Returns the block count."""
+    _req(isinstance(k_cache, Fp8KV) and isinstance(v_cache, Fp8KV), "fp8 KV cache: both k and v must be Fp8KV")
+    _req(D == 128, "fp8 KV cache needs head_dim 128")
+    kd = k_cache.data
+    _req(kd.dim() == 4 and kd.shape[1] == Hkv and kd.shape[2] == 64 and kd.shape[3] == D, "fp8 cache [nb,Hkv,64,128]")
+    for side, c in (("k", k_cache), ("v", v_cache)):
+        _req(c.data.dtype == FP8 and c.data.shape == kd.shape and c.data.is_contiguous() and c.data.is_cuda
+             and c.data.device == dev, "%s cache data must be contiguous e4m3fn on the launch device" % side)
+        _req(c.scale.dtype == torch.float32 and c.scale.shape == kd.shape[:3] and c.scale.is_contiguous()
+             and c.scale.device == dev, "%s cache scales must be contiguous fp32 [nb,Hkv,64] on the cache's device" % side)
+    return kd.shape[0]
 
 
 def _bf16_2d(t, name):
@@ -108,6 +124,8 @@ PREFILL_ROPE_FUSED = os.environ.get("RAGK_PREFILL_ROPE", "1") != "0"
 def gemm_rope_kv_ok(x, w, positions, cos_t, sin_t, slots, k_cache, v_cache, Hq, Hkv, D):
     """Whether gemm_rope_kv takes these operands (else: gemm + rope_kv)."""
     if not PREFILL_ROPE_FUSED or D != 128 or slots is None or k_cache is None or v_cache is None:
+        return False
+    if isinstance(k_cache, Fp8KV) or isinstance(v_cache, Fp8KV):  # the epilogue writes bf16 rows only
         return False
     if not (isinstance(x, torch.Tensor) and isinstance(w, torch.Tensor) and x.is_cuda and w.dim() == 2):
         return False
@@ -790,6 +808,16 @@ def rope_kv(qkv, positions, cos_t, sin_t, slots, k_cache, v_cache, Hq, Hkv, D, a
     T = qkv.shape[0]
     _req(qkv.shape[1] >= (Hq + 2 * Hkv) * D, "qkv width")
     _req(positions.dtype == torch.int32 and positions.numel() == T, "positions")
+    if isinstance(k_cache, Fp8KV) or isinstance(v_cache, Fp8KV):
+        _req(apply_rope, "fp8 KV cache: rope_kv without RoPE is not built")
+        _req(slots is not None and slots.dtype == torch.int32 and slots.numel() == T, "slots")
+        _req(cos_t is not None and sin_t is not None, "rope tables")
+        _kv8(k_cache, v_cache, Hkv, D, qkv.device)
+        check(_lib.lib().ragk_rope_kv_fp8(qkv.data_ptr(), qkv.stride(0), positions.data_ptr(), cos_t.data_ptr(),
+                                          sin_t.data_ptr(), slots.data_ptr(), k_cache.data.data_ptr(),
+                                          v_cache.data.data_ptr(), k_cache.scale.data_ptr(), v_cache.scale.data_ptr(),
+                                          T, Hq, Hkv, D, 64, stream_ptr()), "ragk_rope_kv_fp8")
+        return
     if slots is not None:
         _req(slots.dtype == torch.int32 and slots.numel() == T, "slots")
         _req(k_cache.dim() == 4 and k_cache.shape[1] == Hkv and k_cache.shape[3] == D, "cache layout")
@@ -822,6 +850,14 @@ def rope_kv_partials(P, q_out, positions, cos_t, sin_t, slots, k_cache, v_cache,
     _req(q_out.shape[0] == T and q_out.shape[1] >= Hq * D, "q_out shape")
     _req(positions.dtype == torch.int32 and positions.numel() == T, "positions")
     _req(slots is not None and slots.dtype == torch.int32 and slots.numel() == T, "slots")
+    if isinstance(k_cache, Fp8KV) or isinstance(v_cache, Fp8KV):
+        _kv8(k_cache, v_cache, Hkv, D, P.device)
+        check(_lib.lib().ragk_rope_kv_partials_fp8(P.data_ptr(), S, T, ldp, q_out.data_ptr(), q_out.stride(0),
+                                                   positions.data_ptr(), ptr(cos_t), ptr(sin_t), slots.data_ptr(),
+                                                   k_cache.data.data_ptr(), v_cache.data.data_ptr(),
+                                                   k_cache.scale.data_ptr(), v_cache.scale.data_ptr(), Hq, Hkv, D, 64,
+                                                   stream_ptr()), "ragk_rope_kv_partials_fp8")
+        return
     _req(k_cache.dim() == 4 and k_cache.shape[1] == Hkv and k_cache.shape[3] == D, "cache layout")
     check(_lib.lib().ragk_rope_kv_partials(P.data_ptr(), S, T, ldp, q_out.data_ptr(), q_out.stride(0),
                                            positions.data_ptr(), ptr(cos_t), ptr(sin_t), slots.data_ptr(),
@@ -892,6 +928,18 @@ def attn_prefill(q, k, v, cu_q, kv_lens, tiles, out, Hq, Hkv, D, causal=True, pa
     _req(q.dtype == torch.bfloat16 and q.stride(-1) == 1, "q")
     _req(tiles.dtype == torch.int32 and tiles.is_cuda and tiles.is_contiguous(), "tiles int32 on GPU")
     _req(D in (32, 64, 128), "head_dim must be 32/64/128")
+    if isinstance(k, Fp8KV) or isinstance(v, Fp8KV):
+        _req(paged and causal, "fp8 KV cache: paged causal attention only")
+        _kv8(k, v, Hkv, D, q.device)
+        _req(block_tables is not None and block_tables.dtype == torch.int32, "block_tables int32")
+        _req(block_tables.stride(0) <= 2048, "prefill block tables wider than 2048 blocks (128k tokens)")
+        scale = 1.0 / math.sqrt(D) if scale is None else scale
+        check(_lib.lib().ragk_attn_prefill_fp8(
+            q.data_ptr(), q.stride(0), k.data.data_ptr(), v.data.data_ptr(), k.scale.data_ptr(), v.scale.data_ptr(),
+            block_tables.data_ptr(), block_tables.stride(0), cu_q.data_ptr(), kv_lens.data_ptr(), tiles.data_ptr(),
+            tiles.shape[0], out.data_ptr(), out.stride(0), Hq, Hkv, D, float(scale), stream_ptr()),
+            "ragk_attn_prefill_fp8")
+        return out
     if paged:
         _req(k.dim() == 4 and k.shape[2] == 64 and k.shape[1] == Hkv and k.shape[3] == D, "paged cache [nb,Hkv,64,D]")
         _req(block_tables is not None and block_tables.dtype == torch.int32, "block_tables int32")
@@ -960,7 +1008,10 @@ def _set_decode_nt(B, Hkv):
 def attn_decode(q, k_cache, v_cache, block_tables, kv_lens, out, Hq, Hkv, D, part_tiles, max_parts, ws_o=None,
                 ws_ml=None, scale=None):
     B = kv_lens.numel()
-    _req(k_cache.dim() == 4 and k_cache.shape[2] == 64 and k_cache.shape[3] == D, "paged cache")
+    f8 = isinstance(k_cache, Fp8KV) or isinstance(v_cache, Fp8KV)
+    if f8:
+        _kv8(k_cache, v_cache, Hkv, D, q.device)
+    _req(len(k_cache.shape) == 4 and k_cache.shape[2] == 64 and k_cache.shape[3] == D, "paged cache")
     _req(block_tables.dtype == torch.int32 and block_tables.shape[0] >= B, "block_tables")
     _req(kv_lens.dtype == torch.int32, "kv_lens int32")
     G = Hq // Hkv
@@ -972,6 +1023,13 @@ def attn_decode(q, k_cache, v_cache, block_tables, kv_lens, out, Hq, Hkv, D, par
         _req(ws_o.numel() >= B * Hq * max_parts * D and ws_ml.numel() >= B * Hq * max_parts * 2, "workspace")
     scale = 1.0 / math.sqrt(D) if scale is None else scale
     _set_decode_nt(B, Hkv)
+    if f8:
+        check(_lib.lib().ragk_attn_decode_fp8(
+            q.data_ptr(), q.stride(0), k_cache.data.data_ptr(), v_cache.data.data_ptr(), k_cache.scale.data_ptr(),
+            v_cache.scale.data_ptr(), block_tables.data_ptr(), block_tables.stride(0), kv_lens.data_ptr(), ptr(ws_o),
+            ptr(ws_ml), out.data_ptr(), out.stride(0), B, Hq, Hkv, D, part_tiles, max_parts, float(scale),
+            stream_ptr()), "ragk_attn_decode_fp8")
+        return out
     check(_lib.lib().ragk_attn_decode(
         q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), block_tables.data_ptr(),
         block_tables.stride(0), kv_lens.data_ptr(), ptr(ws_o), ptr(ws_ml), out.data_ptr(), out.stride(0), B, Hq, Hkv,
@@ -990,7 +1048,10 @@ def attn_decode_rope(P, positions, cos_t, sin_t, slots, k_cache, v_cache, block_
     _req(kv_lens.numel() == B, "one partial row per sequence")
     _req(positions.dtype == torch.int32 and positions.numel() == B, "positions")
     _req(slots is not None and slots.dtype == torch.int32 and slots.numel() == B, "slots")
-    _req(k_cache.dim() == 4 and k_cache.shape[1] == Hkv and k_cache.shape[2] == 64 and k_cache.shape[3] == D,
+    f8 = isinstance(k_cache, Fp8KV) or isinstance(v_cache, Fp8KV)
+    if f8:
+        _kv8(k_cache, v_cache, Hkv, D, P.device)
+    _req(len(k_cache.shape) == 4 and k_cache.shape[1] == Hkv and k_cache.shape[2] == 64 and k_cache.shape[3] == D,
          "paged cache")
     _req(block_tables.dtype == torch.int32 and block_tables.shape[0] >= B, "block_tables")
     _req(kv_lens.dtype == torch.int32, "kv_lens int32")
@@ -1008,11 +1069,19 @@ def attn_decode_rope(P, positions, cos_t, sin_t, slots, k_cache, v_cache, block_
     if defer_merge:
         lib.ragk_attn_decode_set_defer(1)
     try:
-        check(lib.ragk_attn_decode_rope(
-            P.data_ptr(), S, ldp, positions.data_ptr(), slots.data_ptr(), cos_t.data_ptr(), sin_t.data_ptr(),
-            k_cache.data_ptr(), v_cache.data_ptr(), block_tables.data_ptr(), block_tables.stride(0),
-            kv_lens.data_ptr(), ptr(ws_o), ptr(ws_ml), out.data_ptr(), out.stride(0), B, Hq, Hkv, D, part_tiles,
-            max_parts, float(scale), stream_ptr()), "ragk_attn_decode_rope")
+        if f8:
+            check(lib.ragk_attn_decode_rope_fp8(
+                P.data_ptr(), S, ldp, positions.data_ptr(), slots.data_ptr(), cos_t.data_ptr(), sin_t.data_ptr(),
+                k_cache.data.data_ptr(), v_cache.data.data_ptr(), k_cache.scale.data_ptr(), v_cache.scale.data_ptr(),
+                block_tables.data_ptr(), block_tables.stride(0), kv_lens.data_ptr(), ptr(ws_o), ptr(ws_ml),
+                out.data_ptr(), out.stride(0), B, Hq, Hkv, D, part_tiles, max_parts, float(scale), stream_ptr()),
+                "ragk_attn_decode_rope_fp8")
+        else:
+            check(lib.ragk_attn_decode_rope(
+                P.data_ptr(), S, ldp, positions.data_ptr(), slots.data_ptr(), cos_t.data_ptr(), sin_t.data_ptr(),
+                k_cache.data_ptr(), v_cache.data_ptr(), block_tables.data_ptr(), block_tables.stride(0),
+                kv_lens.data_ptr(), ptr(ws_o), ptr(ws_ml), out.data_ptr(), out.stride(0), B, Hq, Hkv, D, part_tiles,
+                max_parts, float(scale), stream_ptr()), "ragk_attn_decode_rope")
     finally:
         if defer_merge:
             lib.ragk_attn_decode_set_defer(0)

@@ -13,6 +13,8 @@ import os
 
 import torch
 
+from ..ops.fp8 import kv_cache_dtype_name, kv_cache_torch_dtype
+
 log = logging.getLogger(__name__)
 
 
@@ -26,7 +28,7 @@ def _load_json(p, default=None):
 def kv_blocks_for(model, cfg, device):
     if cfg.kv_cache_blocks > 0:
         return cfg.kv_cache_blocks
-    per = model.kv_bytes_per_block()
+    per = model.kv_bytes_per_block(kv_cache_torch_dtype(cfg.kv_cache_dtype))  # fp8: D + 4 bytes per cached row
     if torch.device(device).type == "cuda":
         free, _ = torch.cuda.mem_get_info(torch.device(device))
         budget = int(free * cfg.kv_cache_fraction)
@@ -68,9 +70,12 @@ def build_generator(cfg, device, tp_rank=0, tp_size=1, comm=None, tp_group=None)
     eos = geos if isinstance(geos, list) else [geos]
     cfg.max_model_len = max_len
     blocks = kv_blocks_for(model, cfg, device)
+    kv_dtype = kv_cache_dtype_name(cfg.kv_cache_dtype)
     engine = LLMEngine(model, num_blocks=blocks, max_batch=cfg.max_batch, max_prefill_tokens=cfg.max_prefill_tokens,
                        max_model_len=max_len, eos_ids=eos, use_graphs=cfg.use_cuda_graphs, tp_group=tp_group,
-                       mixed_prefill_tokens=cfg.mixed_prefill_tokens)
+                       mixed_prefill_tokens=cfg.mixed_prefill_tokens, kv_dtype=kv_dtype)
+    log.info("KV cache: dtype %s, %d blocks of 64 tokens, %.1f MiB", kv_dtype, blocks,
+             blocks * model.kv_bytes_per_block(kv_cache_torch_dtype(kv_dtype)) / 2 ** 20)
     return engine, tok, gen
 
 

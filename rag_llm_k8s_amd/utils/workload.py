@@ -143,9 +143,15 @@ def build_workload(model="8b", embedder="minilm", n_chunks=10000, chunk_words=10
                    max_new_tokens=150, max_batch=32, max_model_len=8192, max_prefill_tokens=32768, device="cuda",
                    ctx=None, tp_comm=None, seed=0, use_graphs=True, index_type="flat", kv_blocks=None,
                    word_vocab=400000, dtype="bf16", index_vectors=0, start_threads=False, ignore_eos=False,
-                   mixed_prefill_tokens=0, progress=None):
+                   mixed_prefill_tokens=0, progress=None, kv_dtype=None):
     """`progress(msg)`: called after each setup stage (bench.py prints it: a 70B / 1M-vector setup runs
-    for minutes)."""
+    for minutes). `kv_dtype`: "bf16" | "fp8" KV cache; None takes the KV_CACHE_DTYPE environment variable
+    (default bf16), so bench.py and tools/bench_serve.py can be A/B-run unmodified."""
+    import os
+
+    from ..ops.fp8 import kv_cache_dtype_name
+
+    kv_dtype = kv_cache_dtype_name(os.environ.get("KV_CACHE_DTYPE") or "bf16" if kv_dtype is None else kv_dtype)
     from ..engine.encoder_engine import EmbeddingEngine
     from ..engine.llm_engine import LLMEngine
     from ..index.store import DocumentStore
@@ -183,7 +189,7 @@ def build_workload(model="8b", embedder="minilm", n_chunks=10000, chunk_words=10
     engine = LLMEngine(m, num_blocks=blocks, max_batch=max_batch, max_prefill_tokens=max_prefill_tokens,
                        max_model_len=max_model_len, eos_ids=lcfg.eos_token_id, use_graphs=use_graphs,
                        tp_group=ctx.tp_group if (ctx is not None and tp_size > 1) else None,
-                       mixed_prefill_tokens=mixed_prefill_tokens)
+                       mixed_prefill_tokens=mixed_prefill_tokens, kv_dtype=kv_dtype)
     ew = E.EncoderWeights.random(ecfg, device, seed=seed + 1)
     emb = EmbeddingEngine(E.EncoderModel(ecfg, ew, device), enc_tok)
     t["weights_s"] = time.time() - t0
@@ -196,7 +202,7 @@ def build_workload(model="8b", embedder="minilm", n_chunks=10000, chunk_words=10
     cfg = RagConfig(device=device, retrieve_k=retrieve_k, context_k=context_k, max_new_tokens=max_new_tokens,
                     max_batch=max_batch, max_model_len=max_model_len, index_path="/tmp/ragk_bench_index",
                     index_type=index_type, seed=seed, max_prefill_tokens=max_prefill_tokens, ignore_eos=ignore_eos,
-                    mixed_prefill_tokens=mixed_prefill_tokens)
+                    mixed_prefill_tokens=mixed_prefill_tokens, kv_cache_dtype=kv_dtype)
     n_index = max(n_chunks, index_vectors)
     store = DocumentStore(cfg.index_path, emb.dim, device=device, index_type=index_type,
                           ivf_nlist=4096 if n_index >= 500_000 else 1024)

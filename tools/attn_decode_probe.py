@@ -9,7 +9,13 @@ Infinity Cache). Prints us per launch and TB/s of KV for each variant:
 variants: base | diag (loads + waits only, no QK^T / softmax / PV: attention.hip DG = 1) | diag_dma (as diag,
 K by 1 KiB LDS-DMA pieces too: DG = 2) | kl (4-wave blocks, K tiles by LDS-DMA: attention.hip KL) | nt0
 (default cache policy). AP_CHECK=1: every variant's output vs the base kernel's. AP_JITTER=n: context lengths uniform in [ctx - n, ctx + n] (the bench's RAG prompts vary).
+
+  python tools/attn_decode_probe.py --kv-dtype fp8  # the fp8 KV cache (e4m3 rows + fp32 row scales, 132 B per row)
+
+fp8 variants: kl (the single-partition grid, K tiles by LDS-DMA: what the engine runs) | base (the same grid on the
+split-K 4-wave kernel, K through registers) | nt0. The diag variants exist for the bf16 cache only.
 """
+import argparse
 import math
 import os
 import sys
@@ -24,6 +30,9 @@ def main():
     from rag_llm_k8s_amd.ops import _lib, native
     from rag_llm_k8s_amd.ops.reference import rope_tables
 
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default=os.environ.get("AP_KV_DTYPE", "bf16"))
+    fp8 = ap.parse_args().kv_dtype == "fp8"
     _build.build_all()
     B = int(os.environ.get("AP_B", "32"))
     ctx = int(os.environ.get("AP_CTX", "5264"))
@@ -56,6 +65,13 @@ def main():
 
     def kv_pair():
         n = nblocks * Hkv * 64 * D
+        if fp8:
+            from rag_llm_k8s_amd.ops.fp8 import Fp8KV, quantize_rows
+
+            def side():
+                q, sc = quantize_rows(torch.randn(nblocks * Hkv * 64, D, device=dev).bfloat16())
+                return Fp8KV(q.view(nblocks, Hkv, 64, D), sc.view(nblocks, Hkv, 64))
+            return side(), side()
         if voff < 0:
             return (torch.randn(nblocks, Hkv, 64, D, device=dev).bfloat16(),
                     torch.randn(nblocks, Hkv, 64, D, device=dev).bfloat16())
@@ -68,17 +84,20 @@ def main():
     P = torch.randn(4, B, (Hq + 2 * Hkv) * D, device=dev) * 0.1
     out = torch.empty(B, Hq * D, device=dev).bfloat16()
     pt, mp = native.decode_partitions(8192, B, Hkv)
-    kv_bytes = sum(lens) * Hkv * D * 2 * 2
-    print("B=%d ctx %d..%d (mean %.0f) NL=%d: %.1f MB of KV per launch, part_tiles %d max_parts %d" % (
-        B, min(lens), max(lens), sum(lens) / B, NL, kv_bytes / 1e6, pt, mp), flush=True)
+    kv_bytes = sum(lens) * Hkv * (D + 4 if fp8 else D * 2) * 2  # fp8: one byte per element + a 4-byte row scale
+    print("kv_dtype=%s B=%d ctx %d..%d (mean %.0f) NL=%d: %.1f MB of KV per launch, part_tiles %d max_parts %d" % (
+        "fp8" if fp8 else "bf16", B, min(lens), max(lens), sum(lens) / B, NL, kv_bytes / 1e6, pt, mp), flush=True)
     L = _lib.lib()
 
     def run():
         for kc, vc in caches:
             native.attn_decode_rope(P, pos, cos, sin, slots, kc, vc, bt, kvl, out, Hq, Hkv, D, pt, mp)
 
-    variants = [v for v in os.environ.get("AP_VARIANTS", "base,diag,base,diag").split(",") if v]
-    if os.environ.get("AP_CHECK") == "1":
+    variants = [v for v in os.environ.get("AP_VARIANTS", "kl,base,kl,base" if fp8 else "base,diag,base,diag").split(",")
+                if v]
+    if fp8 and any(v.startswith("diag") for v in variants):
+        raise SystemExit("the diag variants are built for the bf16 cache only")
+    if os.environ.get("AP_CHECK") == "1" and not fp8:
         outs = {}
         kl_default = native.DECODE_KL
         for v in ("base", "kl"):
