@@ -45,7 +45,7 @@ class RagConfig:
     do_sample: Optional[bool] = None  # None -> generation_config.json (reference: model.generate defaults)
     seed: int = 0
     tp_size: int = 1
-    dtype: str = "bf16"
+    dtype: str = "bf16"  # bf16 | fp8 (e4m3 weights, per-row scales) | mxfp4 (OCP MXFP4 weights; opt-in, lossy)
     device: str = "auto"  # auto | cuda | cpu
     index_type: str = "flat"  # flat | ivf
     ivf_nlist: int = 1024

@@ -220,6 +220,20 @@ class LlamaWeights:
         self.dtype = "fp8"
         return self
 
+    def quantize_mxfp4(self, lm_head=False):
+        """OCP MXFP4 weights (ops/mxfp4.py: e2m1 elements, one E8M0 scale per 32 k) for every linear layer (qkv, o,
+        packed gate/up, down; optionally lm_head). Embedding and norms stay bf16. Works on a TP shard: blocks run
+        along K, and the row-parallel K shards are multiples of 128."""
+        from ..ops.mxfp4 import quantize_weight
+
+        for L in self.layers:
+            for k in ("wqkv", "wo", "wgu", "wdown"):
+                L[k] = quantize_weight(L[k])
+        if lm_head:
+            self.lm_head = quantize_weight(self.lm_head)
+        self.dtype = "mxfp4"
+        return self
+
     def nbytes(self):
         t = [self.embed, self.norm, self.lm_head] + [v for l in self.layers for v in l.values()]
         return sum(x.nbytes() if hasattr(x, "dequant") else x.numel() * x.element_size() for x in t)

@@ -94,6 +94,7 @@ _SIGS = {
     "ragk_gemm_stream_splits": [I, I, I, I],
     "ragk_quant_fp8_rows": [P, I, P, I, P, I, I, S],
     "ragk_gemm_fp8": [P, I, P, I, P, P, I, P, P, I, P, P, I, I, I, I, I, I, S],
+    "ragk_gemm_mxfp4": [P, I, P, I, P, P, I, P, I, P, I, P, P, I, I, I, I, I, I, S],
     # csrc/comm/allreduce.hip (xGMI peer-mapped all-reduce)
     "ragk_ar_create": [I, I, ctypes.c_long, I, I, I],
     "ragk_ar_add_rmsnorm": [P, P, I, I, P, I, P, P, I, I, F, I, S],

@@ -18,9 +18,12 @@ from typing import List, Optional
 import torch
 
 from . import reference as R
+from . import mxfp4
 from .fp8 import Fp8KV, Fp8Weight, reference_linear
+from .mxfp4 import Mxfp4Weight
 
 KV_BLOCK = 64
+_QUANT = (Fp8Weight, Mxfp4Weight)  # weight containers the bf16-only decode fusions refuse
 
 
 @dataclass
@@ -49,6 +52,8 @@ class TorchBackend:
     def gemm(self, x, w, bias=None, resid=None, epi="none", out=None, out_f32=False):
         if isinstance(w, Fp8Weight):
             y = reference_linear(x, w, bias, resid, epi=epi, out_f32=out_f32)
+        elif isinstance(w, Mxfp4Weight):
+            y = mxfp4.reference_linear(x, w, bias, resid, epi=epi, out_f32=out_f32)
         else:
             y = R.linear(x, w, bias, resid, epi=epi, out_f32=out_f32)
         if out is not None:
@@ -124,18 +129,18 @@ class TorchBackend:
     # split-K decode path (GPU: gemm_part.hip + the consumers in norm.hip) ----------------
     enable_part = False  # the torch oracle runs the same dataflow when a test switches it on
 
-    def part_ok(self, M, w):
-        return self.enable_part and M <= 64
+    def part_ok(self, M, w):  # MXFP4 weights: no split-K slabs, the generic per-projection path runs
+        return self.enable_part and M <= 64 and not isinstance(w, Mxfp4Weight)
 
     def gemm_part(self, x, w):
-        wf = w.dequant() if isinstance(w, Fp8Weight) else w.float()
+        wf = w.dequant() if isinstance(w, (Fp8Weight, Mxfp4Weight)) else w.float()
         return (x.float() @ wf.t()).unsqueeze(0)
 
     def part_norm_ok(self, M, w):
-        return self.enable_part and M <= 4 and not isinstance(w, Fp8Weight) and w.shape[1] <= 8192
+        return self.enable_part and M <= 4 and not isinstance(w, _QUANT) and w.shape[1] <= 8192
 
     def part_silu_ok(self, M, w_gu, w_down):
-        return (self.enable_part and M <= 4 and not isinstance(w_gu, Fp8Weight) and not isinstance(w_down, Fp8Weight)
+        return (self.enable_part and M <= 4 and not isinstance(w_gu, _QUANT) and not isinstance(w_down, _QUANT)
                 and w_down.shape[1] % 64 == 0)
 
     def gemm_part_gu(self, x, w):
@@ -152,7 +157,7 @@ class TorchBackend:
         return self.gemm_part(R.rmsnorm(h, gamma, eps), w)
 
     def mlp_engine_ok(self, M, w_gu, w_down):
-        return (self.enable_part and M == 1 and not isinstance(w_gu, Fp8Weight) and not isinstance(w_down, Fp8Weight)
+        return (self.enable_part and M == 1 and not isinstance(w_gu, _QUANT) and not isinstance(w_down, _QUANT)
                 and w_down.shape[1] % 64 == 0)
 
     def mlp_engine(self, xn, w_gu, w_down, h):
@@ -263,6 +268,8 @@ class NativeBackend(TorchBackend):
     def gemm(self, x, w, bias=None, resid=None, epi="none", out=None, out_f32=False):
         if isinstance(w, Fp8Weight):
             return self.n.gemm_fp8(x, w, bias=bias, resid=resid, epi=epi, out=out, out_f32=out_f32)
+        if isinstance(w, Mxfp4Weight):
+            return self.n.gemm_mxfp4(x, w, bias=bias, resid=resid, epi=epi, out=out, out_f32=out_f32)
         return self.n.gemm(x, w, bias=bias, resid=resid, epi=epi, out=out, out_f32=out_f32)
 
     def rmsnorm(self, x, w, eps, out=None):
@@ -296,7 +303,7 @@ class NativeBackend(TorchBackend):
     enable_part = __import__("os").environ.get("RAGK_DECODE_PART", "1") == "1"
 
     def part_ok(self, M, w):
-        if not self.enable_part or M > 64:
+        if not self.enable_part or M > 64 or isinstance(w, Mxfp4Weight):
             return False
         return self.n.gemm_part_slabs(M, w.shape[0], w.shape[1])[1] > 0
 
@@ -304,7 +311,7 @@ class NativeBackend(TorchBackend):
         return self.n.gemm_part(x, w)
 
     def part_norm_ok(self, M, w):
-        return self.enable_part and M <= 4 and not isinstance(w, Fp8Weight) and w.shape[1] in (4096, 8192)
+        return self.enable_part and M <= 4 and not isinstance(w, _QUANT) and w.shape[1] in (4096, 8192)
 
     def gemm_part_norm(self, h, gamma, eps, w):
         return self.n.gemm_part_norm(h, gamma, eps, w)
@@ -344,7 +351,7 @@ class NativeBackend(TorchBackend):
                                        defer_merge=defer_merge)
 
     def prefill_nsplit(self, M, w):
-        if isinstance(w, Fp8Weight):
+        if isinstance(w, _QUANT):
             return 1
         return self.n.prefill_nsplit(M, w.shape[0], w.shape[1])
 
@@ -352,7 +359,7 @@ class NativeBackend(TorchBackend):
         return self.n.gemm_splitk(x, w, nsplit)
 
     def part_merge_ok(self, M, meta: AttnMeta, w, Hq, D):
-        return (self.enable_part and D == 128
+        return (self.enable_part and D == 128 and not isinstance(w, Mxfp4Weight)
                 and self.n.gemm_part_merge_ok(M, w, Hq, meta.max_parts, meta.ws_o))
 
     def gemm_part_merge(self, attn_out, meta: AttnMeta, w, Hq):

@@ -748,6 +748,63 @@ def gemm_fp8(x, w, bias=None, resid=None, epi="none", out=None, out_f32=False):
     return out
 
 
+# ----------------------------------------------------------------------------- MXFP4 GEMM
+def gemm_mxfp4(x, w, bias=None, resid=None, epi="none", out=None, out_f32=False, act=None):
+    """out[M,N] = epi(x[M,K] @ dequant(w)^T) for an :class:`ops.mxfp4.Mxfp4Weight` w (rows = N, or 2N
+    packed gate/up for epi='silu_mul'). M <= 64: W4A16 decode kernel; else W4A8 prefill kernel.
+    act=(q, s): activations already quantized as quant_fp8_rows gives them (e4m3 [M,K], fp32 [M]); the prefill
+    kernel runs on them whatever M is, quant_rows is skipped and x may be None."""
+    from .fp8 import DEC_MAX_M
+
+    if act is None:
+        _bf16_2d(x, "x")
+        M, K = x.shape
+        dev = x.device
+    else:
+        q, sa = act
+        _req(q.dtype == torch.float8_e4m3fn and q.is_cuda and q.dim() == 2 and q.stride(1) == 1
+             and q.stride(0) % 16 == 0 and q.data_ptr() % 16 == 0, "act q e4m3 [M,K], 16-byte aligned rows")
+        M, K = q.shape
+        _req(sa.dtype == torch.float32 and sa.is_cuda and sa.is_contiguous() and sa.numel() == M, "act scale fp32[M]")
+        dev = q.device
+    w4, sw = w.packed, w.scale
+    _req(w4.dtype == torch.uint8 and w4.is_cuda and w4.is_contiguous() and w4.shape[1] * 2 == K, "mxfp4 weight")
+    _req(sw.dtype == torch.uint8 and sw.is_cuda and sw.is_contiguous() and sw.shape == (w4.shape[0], K // 32),
+         "mxfp4 scale")
+    _req(K % 128 == 0, "K must be a multiple of 128")
+    e = EPI[epi]
+    N = w4.shape[0] // 2 if epi == "silu_mul" else w4.shape[0]
+    dec = act is None and M <= DEC_MAX_M
+    if epi == "silu_mul":
+        _req(N % 64 == 0 and not out_f32, "silu_mul needs N % 64 == 0, bf16 out")
+    elif not dec:
+        _req(N % 8 == 0, "N % 8")
+    if "bias" in epi:
+        _req(bias is not None and bias.dtype == torch.bfloat16 and bias.numel() == N, "bias bf16[N]")
+    if "resid" in epi:
+        _bf16_2d(resid, "resid")
+        _req(resid.shape == (M, N), "resid shape")
+    odt = torch.float32 if out_f32 else torch.bfloat16
+    out = torch.empty((M, N), dtype=odt, device=dev) if out is None else out
+    _req(out.dtype == odt and out.shape == (M, N) and out.stride(1) == 1, "out shape/dtype")
+    if not dec:  # the prefill kernel stores 8 columns (16 / 32 bytes) at a time
+        _req(out.stride(0) % 8 == 0 and out.data_ptr() % 16 == 0, "out rows 16-byte aligned")
+    if M == 0:
+        return out
+    ldr = resid.stride(0) if resid is not None else 0
+    if dec:
+        rc = _lib.lib().ragk_gemm_mxfp4(x.data_ptr(), x.stride(0), None, 0, None, w4.data_ptr(), w4.stride(0),
+                                        sw.data_ptr(), sw.stride(0), out.data_ptr(), out.stride(0), ptr(bias),
+                                        ptr(resid), ldr, M, N, K, e, int(out_f32), stream_ptr())
+    else:
+        q, sa = quant_fp8_rows(x) if act is None else act
+        rc = _lib.lib().ragk_gemm_mxfp4(None, 0, q.data_ptr(), q.stride(0), sa.data_ptr(), w4.data_ptr(),
+                                        w4.stride(0), sw.data_ptr(), sw.stride(0), out.data_ptr(), out.stride(0),
+                                        ptr(bias), ptr(resid), ldr, M, N, K, e, int(out_f32), stream_ptr())
+    check(rc, "ragk_gemm_mxfp4")
+    return out
+
+
 # ----------------------------------------------------------------------------- norms
 def rmsnorm(x, w, eps, out=None, resid=None):
     _bf16_2d(x, "x")

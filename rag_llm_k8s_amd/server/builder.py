@@ -45,6 +45,8 @@ def build_generator(cfg, device, tp_rank=0, tp_size=1, comm=None, tp_group=None)
     mcfg = _load_json(os.path.join(cfg.model_path, "config.json"))
     if mcfg is None:
         raise FileNotFoundError("no config.json under MODEL_PATH=%s" % cfg.model_path)
+    if cfg.dtype == "mxfp4" and mcfg.get("model_type", "llama") == "gpt2":
+        raise ValueError("DTYPE=mxfp4 covers Llama-family checkpoints only; this GPT-2 checkpoint serves DTYPE=bf16")
     gen = _load_json(os.path.join(cfg.model_path, "generation_config.json"), {})
     tok = Tokenizer(cfg.model_path)
     mt = mcfg.get("model_type", "llama")
@@ -63,6 +65,10 @@ def build_generator(cfg, device, tp_rank=0, tp_size=1, comm=None, tp_group=None)
         w = LlamaWeights.from_checkpoint(cfg.model_path, c, device, tp_rank, tp_size)
         if cfg.dtype == "fp8":  # DTYPE=fp8: e4m3fn linear weights, per-row scales (BASELINE config 5)
             w.quantize_fp8()
+        elif cfg.dtype == "mxfp4":  # DTYPE=mxfp4: OCP MXFP4 linear weights, applied to this rank's shard (opt-in, lossy)
+            w.quantize_mxfp4()
+            if torch.device(device).type == "cuda":
+                torch.cuda.empty_cache()  # hand the bf16 originals back before kv_blocks_for reads the free HBM
         max_len = min(cfg.max_model_len, c.max_position_embeddings)
         model = LlamaModel(c, w, device, comm=comm, max_positions=max_len)
         eos = c.eos_token_id

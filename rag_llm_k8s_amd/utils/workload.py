@@ -184,6 +184,10 @@ def build_workload(model="8b", embedder="minilm", n_chunks=10000, chunk_words=10
         w.quantize_fp8()
         if device.startswith("cuda"):
             torch.cuda.empty_cache()
+    elif dtype == "mxfp4":  # OCP MXFP4 linear weights (bf16 embeddings / norms / lm_head)
+        w.quantize_mxfp4()
+        if device.startswith("cuda"):
+            torch.cuda.empty_cache()
     m = L.LlamaModel(lcfg, w, device, comm=tp_comm, max_positions=max_model_len)
     blocks = kv_blocks or (max_batch * (-(-max_model_len // 64)) + 16)
     engine = LLMEngine(m, num_blocks=blocks, max_batch=max_batch, max_prefill_tokens=max_prefill_tokens,

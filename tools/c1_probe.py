@@ -1,6 +1,8 @@
 """Single-query (C=1) latency anatomy of the served RAG path on one GPU (bench.py's config-2 workload):
 query embed, index search, prompt build + tokenize, the prefill step (first token) and the decode
-steps, each bracketed by torch.cuda.synchronize(). Prints ms per phase (median of N queries)."""
+steps, each bracketed by torch.cuda.synchronize(). Prints ms per phase (median of N queries).
+--dtype {bf16,fp8,mxfp4} picks the linear-weight mode (default bf16)."""
+import argparse
 import os
 import sys
 import time
@@ -17,11 +19,14 @@ def main():
     from rag_llm_k8s_amd.parallel import dist as D
     from rag_llm_k8s_amd.utils.workload import build_workload, make_queries
 
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8", "mxfp4"])
+    a = ap.parse_args()
     _build.build_all()
     ctx = D.init_distributed(tp=1)
     wl = build_workload(model="8b", embedder="minilm", n_chunks=10000, retrieve_k=4,
                         context_k=4, max_new_tokens=150, max_batch=32, device=ctx.device, ctx=ctx, tp_comm=None,
-                        seed=0, use_graphs=True, index_type="flat", dtype="bf16", index_vectors=0)
+                        seed=0, use_graphs=True, index_type="flat", dtype=a.dtype, index_vectors=0)
     svc = wl.svc
     eng = svc.engine
     eng.warmup_graphs()
@@ -55,9 +60,9 @@ def main():
             rows.append([(t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (t4 - t3) * 1e3, (t5 - t4) * 1e3,
                          (t5 - t0) * 1e3, len(ids), len(s.out)])
     med = [sorted(r[k] for r in rows)[len(rows) // 2] for k in range(8)]
-    print("C=1 anatomy (median of %d): embed %.2f ms, search %.2f ms, prompt+tokenize %.2f ms, prefill->first "
+    print("C=1 anatomy, %s weights (%.2f GB) (median of %d): embed %.2f ms, search %.2f ms, prompt+tokenize %.2f ms, prefill->first "
           "token %.2f ms, decode %.2f ms (%d tokens, %.3f ms/token), total %.1f ms, prompt %d tokens" % (
-              len(rows), med[0], med[1], med[2], med[3], med[4], med[7] - 1, med[4] / max(1, med[7] - 1), med[5],
+              a.dtype, eng.model.w.nbytes() / 1e9, len(rows), med[0], med[1], med[2], med[3], med[4], med[7] - 1, med[4] / max(1, med[7] - 1), med[5],
               med[6]), flush=True)
 
 
