@@ -43,6 +43,17 @@ def _bf16_2d(t, name):
     _req(t.stride(1) == 1, "%s must be row-contiguous" % name)
 
 
+def _al16(t, name):
+    """An operand the kernel touches with 16-byte vector, buffer or LDS-DMA accesses: its base pointer and
+    (with more than one row) its row pitch must be multiples of 16 bytes. A misaligned view faults or
+    silently reads the wrong bytes, so it is refused here, before the launch."""
+    if t is None:
+        return
+    _req(t.data_ptr() % 16 == 0, "%s: base pointer must be 16-byte aligned (column offset of a view?)" % name)
+    _req(t.dim() < 2 or t.shape[0] <= 1 or (t.stride(0) * t.element_size()) % 16 == 0,
+         "%s: row pitch must be a multiple of 16 bytes (got %d elements)" % (name, t.stride(0) if t.dim() > 1 else 0))
+
+
 # ----------------------------------------------------------------------------- GEMM
 # large-M GEMMs (prefill) go to the 256x256 MFMA kernels from this many rows
 PP_MIN_M = 1024
@@ -199,6 +210,9 @@ def gemm(x, w, bias=None, resid=None, epi="none", out=None, out_f32=False, path=
         raise ValueError("tile GEMM needs N % 8 == 0")
     if M == 0:
         return out
+    # every kernel of the family fetches x and w as 16-byte fragments / LDS-DMA pieces
+    _al16(x, "x")
+    _al16(w, "w")
     L = _lib.lib()
     ldr = resid.stride(0) if resid is not None else 0
     if (path is None and PREFILL_BLAS != "none" and not out_f32 and bias is None and use_pp(M, N, K, epi)
@@ -214,6 +228,16 @@ def gemm(x, w, bias=None, resid=None, epi="none", out=None, out_f32=False, path=
         path = 5
     if path is None and DEC_DEFAULT and use_dec(M, N, K, epi):
         path = 4
+    _req(path in (None, 0, 1, 2, 3, 4, 5, 6), "unknown GEMM path %r" % (path,))
+    if path in (0, 2, 6) or (path is None and M > 64):
+        # tile epilogues (gemm_tile, gemm_pp, gemm_w4) store 8 columns at a time and read bias / resid as
+        # 16-byte vectors; the decode kernels (skinny / gemv, gemm_dec, gemm_stream: paths 1, 3, 4, 5 and the
+        # default route at M <= 64) touch them element by element
+        _al16(out, "out")
+        if "bias" in epi:
+            _al16(bias, "bias")
+        if "resid" in epi:
+            _al16(resid, "resid")
     if path == 5:
         rc = _gemm_stream(x, w, None, out, bias, resid, ldr, M, N, K, epi, e, out_f32)
     elif path == 4:
@@ -269,6 +293,9 @@ def gemm_part_norm(h, gamma, eps, w, out=None, ks=None):
     if ks not in (8, 16):  # the norm variant is built for 8- and 16-step K-slices
         ks, S = gemm_part_slabs(1, N, K, 16)
     _req(S > 0 and K in (4096, 8192), "gemm_part_norm: unsupported K=%d" % K)
+    _al16(h, "h")
+    _al16(w, "w")
+    _al16(gamma, "gamma")
     if out is None:
         out = torch.empty((S, M, N), dtype=torch.float32, device=h.device)
     check(_lib.lib().ragk_gemm_part_norm(h.data_ptr(), h.stride(0), gamma.data_ptr(), float(eps), w.data_ptr(),
@@ -322,8 +349,12 @@ def gemm_stream_part(x, w, out=None, rows=None, S=None):
     r0, s0 = stream_part_cfg(M, N, K)
     rows, S = rows or r0, S or s0
     _req(rows in (64, 128) and S >= 1 and (K // 64) % S == 0, "gemm_stream_part config")
+    _al16(x, "x")  # x and w arrive by LDS-DMA, 16 bytes per lane
+    _al16(w, "w")
     if out is None:
         out = torch.empty((S, M, N), dtype=torch.float32, device=x.device)
+    _req(out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= S * M * N and out.data_ptr() % 16 == 0,
+         "gemm_stream_part out: contiguous fp32 [S, M, N], 16-byte aligned")
     check(_lib.lib().ragk_gemm_stream_part(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), M, N,
                                            K, S, rows, stream_ptr()), "ragk_gemm_stream_part")
     return out
@@ -347,6 +378,8 @@ def gemm_part(x, w, out=None, ks=None):
     M, K = x.shape
     N = wt.shape[0]
     _req(wt.shape[1] == K and M <= 64, "gemm_part shape %s x %s" % (tuple(x.shape), tuple(wt.shape)))
+    _al16(x, "x")  # LDS-DMA staging of the activation slice, 16-byte weight fragments
+    _al16(wt, "w")
     if (STREAM_PART and not fp8 and ks is None and out is None and M >= STREAM_PART_MIN_M and K % 64 == 0
             and N % 4 == 0 and stream_part_cfg(M, N, K)[1] > 0):
         return gemm_stream_part(x, wt)
@@ -354,7 +387,7 @@ def gemm_part(x, w, out=None, ks=None):
     _req(S > 0, "gemm_part: unsupported K=%d" % K)
     if out is None:
         out = torch.empty((S, M, N), dtype=torch.float32, device=x.device)
-    _req(out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= S * M * N, "gemm_part out")
+    _req(out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= S * M * N, "gemm_part out")  # scalar stores
     if fp8:
         check(_lib.lib().ragk_gemm_part_fp8(x.data_ptr(), x.stride(0), wt.data_ptr(), wt.stride(0),
                                             w.scale.data_ptr(), out.data_ptr(), M, N, K, ks, stream_ptr()),
@@ -411,7 +444,10 @@ def gemm_splitk(x, w, nsplit, out=None):
     _req(w.shape[1] == K and K % (64 * nsplit) == 0 and K // nsplit >= 256 and N % 8 == 0, "gemm_splitk shape")
     if out is None:
         out = torch.empty((nsplit, M, N), dtype=torch.float32, device=x.device)
-    _req(out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= nsplit * M * N, "gemm_splitk out")
+    _req(out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= nsplit * M * N
+         and out.data_ptr() % 16 == 0, "gemm_splitk out: contiguous fp32 slabs, 16-byte aligned")
+    _al16(x, "x")  # buffer LDS-DMA operands, 16-byte slab stores
+    _al16(w, "w")
     check(_lib.lib().ragk_gemm_w4_splitk(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), M, N, K,
                                          nsplit, stream_ptr()), "ragk_gemm_w4_splitk")
     return out
@@ -697,6 +733,8 @@ def quant_fp8_rows(x, q=None, scale=None):
     q = torch.empty((M, K), dtype=torch.float8_e4m3fn, device=x.device) if q is None else q
     scale = torch.empty(M, dtype=torch.float32, device=x.device) if scale is None else scale
     _req(q.shape == (M, K) and q.is_contiguous() and scale.numel() == M, "quant buffers")
+    _al16(x, "x")  # rows are read as 16-byte vectors and written as 8-byte ones
+    _req(q.data_ptr() % 8 == 0, "q: base pointer must be 8-byte aligned")
     check(_lib.lib().ragk_quant_fp8_rows(x.data_ptr(), x.stride(0), q.data_ptr(), q.stride(0), scale.data_ptr(), M, K,
                                          stream_ptr()), "ragk_quant_fp8_rows")
     return q, scale
@@ -705,42 +743,63 @@ def quant_fp8_rows(x, q=None, scale=None):
 FP8_DEC_STREAM = True
 
 
-def gemm_fp8(x, w, bias=None, resid=None, epi="none", out=None, out_f32=False):
+def gemm_fp8(x, w, bias=None, resid=None, epi="none", out=None, out_f32=False, act=None):
     """out[M,N] = epi(x[M,K] @ dequant(w)^T) for an :class:`ops.fp8.Fp8Weight` w (rows = N, or 2N
-    packed gate/up for epi='silu_mul'). M <= 64: W8A16 decode kernel; else W8A8 prefill kernel."""
+    packed gate/up for epi='silu_mul'). M <= 64: W8A16 decode kernel; else W8A8 prefill kernel.
+    act=(q, s): activations already quantized as quant_fp8_rows gives them (e4m3 [M,K], fp32 [M]); the prefill
+    kernel runs on them whatever M is, quant_rows is skipped and x may be None."""
     from .fp8 import DEC_MAX_M
 
-    _bf16_2d(x, "x")
-    M, K = x.shape
+    if act is None:
+        _bf16_2d(x, "x")
+        _al16(x, "x")  # 16-byte fragments (decode) / 16-byte row vectors (quant_rows)
+        M, K = x.shape
+        dev = x.device
+    else:
+        q, sa = act
+        _req(q.dtype == torch.float8_e4m3fn and q.is_cuda and q.dim() == 2 and q.stride(1) == 1
+             and q.stride(0) % 16 == 0 and q.data_ptr() % 16 == 0, "act q e4m3 [M,K], 16-byte aligned rows")
+        M, K = q.shape
+        _req(sa.dtype == torch.float32 and sa.is_cuda and sa.is_contiguous() and sa.numel() == M, "act scale fp32[M]")
+        dev = q.device
     w8, sw = w.w8, w.scale
-    _req(w8.dtype == torch.float8_e4m3fn and w8.is_cuda and w8.is_contiguous() and w8.shape[1] == K, "fp8 weight")
-    _req(sw.dtype == torch.float32 and sw.numel() == w8.shape[0], "fp8 scale")
+    _req(w8.dtype == torch.float8_e4m3fn and w8.is_cuda and w8.is_contiguous() and w8.shape[1] == K
+         and w8.data_ptr() % 16 == 0, "fp8 weight: contiguous e4m3 [rows, K], 16-byte aligned")
+    _req(sw.dtype == torch.float32 and sw.is_cuda and sw.is_contiguous() and sw.numel() == w8.shape[0], "fp8 scale")
     _req(K % 128 == 0, "K must be a multiple of 128")
     e = EPI[epi]
     N = w8.shape[0] // 2 if epi == "silu_mul" else w8.shape[0]
+    dec = act is None and M <= DEC_MAX_M
     if epi == "silu_mul":
         _req(N % 64 == 0 and not out_f32, "silu_mul needs N % 64 == 0, bf16 out")
-    elif M > DEC_MAX_M:
+    elif not dec:
         _req(N % 8 == 0, "N % 8")
     if "bias" in epi:
-        _req(bias is not None and bias.dtype == torch.bfloat16 and bias.numel() == N, "bias bf16[N]")
+        _req(bias is not None and bias.is_cuda and bias.dtype == torch.bfloat16 and bias.numel() == N
+             and bias.is_contiguous(), "bias bf16[N]")
     if "resid" in epi:
         _bf16_2d(resid, "resid")
         _req(resid.shape == (M, N), "resid shape")
     odt = torch.float32 if out_f32 else torch.bfloat16
-    out = torch.empty((M, N), dtype=odt, device=x.device) if out is None else out
+    out = torch.empty((M, N), dtype=odt, device=dev) if out is None else out
     _req(out.dtype == odt and out.shape == (M, N) and out.stride(1) == 1, "out shape/dtype")
+    if not dec:  # the prefill kernel stores 8 columns at a time and reads bias / resid as 16-byte vectors
+        _al16(out, "out")
+        if "bias" in epi:
+            _al16(bias, "bias")
+        if "resid" in epi:
+            _al16(resid, "resid")
     if M == 0:
         return out
     ldr = resid.stride(0) if resid is not None else 0
-    if M <= DEC_MAX_M and FP8_DEC_STREAM and use_stream(M, N, K, epi, fp8=True):
+    if dec and FP8_DEC_STREAM and use_stream(M, N, K, epi, fp8=True):
         rc = _gemm_stream(x, w8, sw, out, bias, resid, ldr, M, N, K, epi, e, out_f32)
-    elif M <= DEC_MAX_M:
+    elif dec:
         rc = _lib.lib().ragk_gemm_fp8(x.data_ptr(), x.stride(0), None, 0, None, w8.data_ptr(), w8.stride(0),
                                       sw.data_ptr(), out.data_ptr(), out.stride(0), ptr(bias), ptr(resid), ldr, M, N,
                                       K, e, int(out_f32), stream_ptr())
     else:
-        q, sa = quant_fp8_rows(x)
+        q, sa = quant_fp8_rows(x) if act is None else act
         rc = _lib.lib().ragk_gemm_fp8(None, 0, q.data_ptr(), q.stride(0), sa.data_ptr(), w8.data_ptr(), w8.stride(0),
                                       sw.data_ptr(), out.data_ptr(), out.stride(0), ptr(bias), ptr(resid), ldr, M, N,
                                       K, e, int(out_f32), stream_ptr())
@@ -815,6 +874,12 @@ def rmsnorm(x, w, eps, out=None, resid=None):
         _bf16_2d(resid, "resid")
         _req(resid.shape == x.shape, "resid shape")
     out = torch.empty_like(x) if out is None else out
+    _req(out.is_cuda and out.dtype == torch.bfloat16 and out.shape == x.shape and out.stride(1) == 1, "out shape/dtype")
+    # the kernel reads x / resid / w and writes resid / out as 8-column (16-byte) vectors
+    _al16(x, "x")
+    _al16(resid, "resid")
+    _al16(w, "weight")
+    _al16(out, "out")
     check(_lib.lib().ragk_rmsnorm(x.data_ptr(), x.stride(0), ptr(resid), resid.stride(0) if resid is not None else 0,
                                   w.data_ptr(), out.data_ptr(), out.stride(0), T, H, float(eps), stream_ptr()),
           "ragk_rmsnorm")
@@ -892,6 +957,8 @@ def add_partials_rmsnorm(P, h, w, eps, out=None):
     _req(w.is_cuda and w.dtype == torch.bfloat16 and w.numel() == H, "norm weight")
     out = torch.empty_like(h) if out is None else out
     _req(out.shape == (M, H) and out.stride(1) == 1, "out")
+    for t, name in ((P, "partials"), (h, "h"), (w, "norm weight"), (out, "out")):  # 16-byte vectors throughout
+        _al16(t, name)
     check(_lib.lib().ragk_add_partials_rmsnorm(P.data_ptr(), P.shape[0], M, h.data_ptr(), h.stride(0), w.data_ptr(),
                                                out.data_ptr(), out.stride(0), H, float(eps), stream_ptr()),
           "ragk_add_partials_rmsnorm")
@@ -907,6 +974,9 @@ def rope_kv_partials(P, q_out, positions, cos_t, sin_t, slots, k_cache, v_cache,
     _req(q_out.shape[0] == T and q_out.shape[1] >= Hq * D, "q_out shape")
     _req(positions.dtype == torch.int32 and positions.numel() == T, "positions")
     _req(slots is not None and slots.dtype == torch.int32 and slots.numel() == T, "slots")
+    # slab rows are summed as f32x4 pairs, q rows stored as 16-byte vectors
+    _req(P.data_ptr() % 16 == 0 and ldp % 4 == 0, "partials: 16-byte aligned rows")
+    _al16(q_out, "q_out")
     if isinstance(k_cache, Fp8KV) or isinstance(v_cache, Fp8KV):
         _kv8(k_cache, v_cache, Hkv, D, P.device)
         check(_lib.lib().ragk_rope_kv_partials_fp8(P.data_ptr(), S, T, ldp, q_out.data_ptr(), q_out.stride(0),
