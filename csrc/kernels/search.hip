@@ -104,6 +104,28 @@ __device__ __forceinline__ void wave_offer_multi(float (&bv)[NQ], int (&bi)[NQ],
     for (int q = 0; q < NQ; ++q) cx(bv[q], bi[q], lane, j, true);
 }
 
+// Filtered search (the MASKED instantiations): query j may only return ids whose bit is set in row
+// qmask[j] of the bitmaps masks[n_masks][stride] (bit id & 31 of word id >> 5); qmask[j] < 0 = no
+// filter. The bit is looked up by the id the kernel REPORTS (ids_map[row], or the row), so one bitmap
+// serves the flat and the IVF store; an id outside [0, bits) is not allowed, so a short bitmap is
+// never read out of bounds. A row that is not allowed becomes the padding candidate (FLT_MAX, -1)
+// for that query only: the masked kernels carry one id per query (a shared id with distance FLT_MAX
+// would sort BEFORE the padding and come out as a result when fewer than k rows are allowed).
+struct RowMask {
+  const unsigned* masks;
+  const int* qmask;
+  int stride;  // words per bitmap row
+  int bits;    // ids covered by a row (<= 32 * stride)
+};
+
+// The word holding id's bit in mask row mr (all ones: unfiltered query; 0: row not live or id
+// outside the bitmap -- no load is issued for those).
+__device__ __forceinline__ unsigned mask_word(const RowMask& m, int mr, bool ok, int id) {
+  if (mr < 0) return ok ? ~0u : 0u;
+  return (ok && (unsigned)id < (unsigned)m.bits) ? m.masks[(size_t)mr * m.stride + (id >> 5)] : 0u;
+}
+__device__ __forceinline__ bool mask_bit(unsigned w, int id) { return (w >> (id & 31)) & 1u; }
+
 // Distances of rows [rbase, rbase + 64) (one per lane; rows clamped into [0, cap)) over dims
 // [t0, t1) of the staged chunk starting at dim dc, for QB queries.
 template <int QB, int U = (QB <= 2 ? 32 : UNR)>
@@ -136,11 +158,12 @@ __device__ __forceinline__ void scan_dims(const float* __restrict__ xt, size_t c
 // Flat scan. Row tile = 64 * (4 / S) rows: wave w scans rows 64 * (w / S) .. +63 of the tile over
 // dim slice w % S of every 256-dim chunk. Block bx handles tiles bx, bx + gridDim.x, ...; its
 // queries are q0 = blockIdx.y * QB .. + QB. Output: per query one sorted list of k at [q][bx].
-template <int QB, int S>
+// MASKED: the filtered variant (RowMask above); the unmasked instantiation never reads mk.
+template <int QB, int S, bool MASKED = false>
 __global__ __launch_bounds__(ST) void l2_scan_kernel(const float* __restrict__ xt, int cap, int d, int row_begin,
                                                      int row_end, int ntiles, const float* __restrict__ q, int nq,
                                                      int k, float* __restrict__ out_d, int* __restrict__ out_i,
-                                                     const int* __restrict__ ids_map) {
+                                                     const int* __restrict__ ids_map, RowMask mk) {
   constexpr int RG = 4 / S;
   constexpr int RB = 64 * RG;
   extern __shared__ __attribute__((aligned(16))) float sc_smem[];
@@ -158,12 +181,27 @@ __global__ __launch_bounds__(ST) void l2_scan_kernel(const float* __restrict__ x
     bv[j] = FLT_MAX;
     bi[j] = -1;
   }
+  int mr[MASKED ? QB : 1];  // block-uniform: the mask row of each query
+  if constexpr (MASKED) {
+#pragma unroll
+    for (int j = 0; j < QB; ++j) mr[j] = j < nqb ? mk.qmask[q0 + j] : -1;
+  }
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int row = row_begin + tile * RB + 64 * g + lane;
     const int rc = min(row, cap - 1);  // rows in [row_end, cap) are valid memory; masked below
     float acc[QB];
 #pragma unroll
     for (int j = 0; j < QB; ++j) acc[j] = 0.f;
+    // the mask words are requested before the dimension loop (one dword per query; the 64 rows of
+    // a wave share two of them when ids are rows) and tested after it
+    unsigned mw[MASKED ? QB : 1];
+    int mid = -1;
+    if constexpr (MASKED) {
+      const bool ok = row < row_end && s == 0;  // (wave-uniform s: only the list-holding waves look)
+      mid = ok ? (ids_map ? ids_map[row] : row) : -1;
+#pragma unroll
+      for (int j = 0; j < QB; ++j) mw[j] = mask_word(mk, mr[j], ok && j < nqb, mid);
+    }
     for (int dc = 0; dc < d; dc += DCH) {
       const int dn = min(DCH, d - dc);
       __syncthreads();  // previous chunk (and the previous tile's slice reduction) consumed
@@ -189,7 +227,18 @@ __global__ __launch_bounds__(ST) void l2_scan_kernel(const float* __restrict__ x
           for (int j = 0; j < QB; ++j) acc[j] += red[(((ss - 1) * RG + g) * QB + j) * 64 + lane];
       }
     }
-    if (s == 0) {  // wave-uniform
+    if constexpr (MASKED) {
+      if (s == 0) {  // wave-uniform
+        int ix[QB];
+#pragma unroll
+        for (int j = 0; j < QB; ++j) {
+          const bool al = mask_bit(mw[j], mid);  // 0 words for dead rows and queries >= nqb
+          acc[j] = al ? acc[j] : FLT_MAX;
+          ix[j] = al ? mid : -1;
+        }
+        wave_offer_multi<QB>(bv, bi, acc, ix, k, lane);
+      }
+    } else if (s == 0) {  // wave-uniform
       const bool ok = row < row_end;
       const int id = ok ? (ids_map ? ids_map[row] : row) : -1;
 #pragma unroll
@@ -238,11 +287,11 @@ __host__ __device__ inline int mq_region0(int d, int QT) {
   return max(min(d, MQ_DCH) * 16 * QT, 2 * 16 * QT * 128);
 }
 
-template <int QT, int RT>
+template <int QT, int RT, bool MASKED = false>
 __global__ __launch_bounds__(ST) void l2_mfma_kernel(const float* __restrict__ xt, int cap, int d, int row_begin,
                                                      int row_end, int ntiles, const float* __restrict__ q, int nq,
                                                      int k, float* __restrict__ out_d, int* __restrict__ out_i,
-                                                     const int* __restrict__ ids_map) {
+                                                     const int* __restrict__ ids_map, RowMask mk) {
   extern __shared__ __attribute__((aligned(16))) float mq_smem[];
   float* qsT = mq_smem;                              // [MQ_DCH][16 * QT]: q transposed, one dim chunk
   float* cd = mq_smem;                               // [16 * QT][128] candidates (merge, aliases qsT)
@@ -291,6 +340,11 @@ __global__ __launch_bounds__(ST) void l2_mfma_kernel(const float* __restrict__ x
   float qnv[QT];
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) qnv[qt] = qn[16 * qt + fr];
+  int mrq[QT];  // MASKED: the mask row of this lane's query of each tile
+  if constexpr (MASKED) {
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) mrq[qt] = 16 * qt + fr < nqb ? mk.qmask[q0 + 16 * qt + fr] : -1;
+  }
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int rbase = row_begin + tile * (64 * RT) + 16 * RT * w;
     int rc[RT];
@@ -393,10 +447,13 @@ __global__ __launch_bounds__(ST) void l2_mfma_kernel(const float* __restrict__ x
         const float xn = xnl[w * 16 * RT + rl];
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
-          const float dv = ok ? fmaxf(xn + qnv[qt] - 2.f * acc[rt][qt][r], 0.f) : FLT_MAX;
-          if (cand_lt(dv, id, lv[qt][MQ_MK - 1], lix[qt][MQ_MK - 1])) {  // insert (rare once warm)
+          // MASKED: a row this query may not return is its padding candidate (FLT_MAX, -1)
+          const bool al = MASKED ? mask_bit(mask_word(mk, mrq[qt], ok, id), id) : ok;
+          const int idq = MASKED ? (al ? id : -1) : id;
+          const float dv = al ? fmaxf(xn + qnv[qt] - 2.f * acc[rt][qt][r], 0.f) : FLT_MAX;
+          if (cand_lt(dv, idq, lv[qt][MQ_MK - 1], lix[qt][MQ_MK - 1])) {  // insert (rare once warm)
             float cv = dv;
-            int cidx = id;
+            int cidx = idq;
 #pragma unroll
             for (int m = 0; m < MQ_MK; ++m) {
               if (cand_lt(cv, cidx, lv[qt][m], lix[qt][m])) {
@@ -482,11 +539,13 @@ __global__ __launch_bounds__(ST) void l2_mfma_kernel(const float* __restrict__ x
 // [offsets[list], ends[list]); packed lists when ends == nullptr: end = offsets[list + 1]) in
 // 256-row tiles (one wave per 64 rows) -> one sorted list of k at [qi][p].
 constexpr int IVF_DMAX = 2048;
+template <bool MASKED = false>
 __global__ __launch_bounds__(ST) void ivf_scan_kernel(const float* __restrict__ xt, int cap, int d,
                                                       const float* __restrict__ q, const int* __restrict__ probes,
                                                       int nprobe, const int* __restrict__ offsets,
                                                       const int* __restrict__ ends, const int* __restrict__ ids_map,
-                                                      int k, float* __restrict__ out_d, int* __restrict__ out_i) {
+                                                      int k, float* __restrict__ out_d, int* __restrict__ out_i,
+                                                      RowMask mk) {
   __shared__ float qs[IVF_DMAX];
   __shared__ float mv[4][64];
   __shared__ int mi[4][64];
@@ -499,10 +558,17 @@ __global__ __launch_bounds__(ST) void ivf_scan_kernel(const float* __restrict__ 
   __syncthreads();
   float bv = FLT_MAX;
   int bi = -1;
+  const int mr = MASKED ? mk.qmask[qi] : -1;  // block-uniform
   for (int r0 = lbeg; r0 < lend; r0 += 4 * 64) {
     const int row = r0 + 64 * w + lane;
     const int rc = min(row, cap - 1);
     float acc = 0.f;
+    unsigned mw = 0;  // MASKED: the id and its mask word are requested before the dimension loop
+    int mid = -1;
+    if constexpr (MASKED) {
+      mid = row < lend ? ids_map[row] : -1;
+      mw = mask_word(mk, mr, row < lend, mid);
+    }
     const float* col = xt + rc;
     int t = 0;
     for (; t + UNR <= d; t += UNR, col += (size_t)UNR * cap) {
@@ -519,8 +585,13 @@ __global__ __launch_bounds__(ST) void ivf_scan_kernel(const float* __restrict__ 
       const float df = *col - qs[t];
       acc = fmaf(df, df, acc);
     }
-    const bool ok = row < lend;
-    wave_offer(bv, bi, ok ? acc : FLT_MAX, ok ? ids_map[row] : -1, k, lane);
+    if constexpr (MASKED) {
+      const bool al = mask_bit(mw, mid);
+      wave_offer(bv, bi, al ? acc : FLT_MAX, al ? mid : -1, k, lane);
+    } else {
+      const bool ok = row < lend;
+      wave_offer(bv, bi, ok ? acc : FLT_MAX, ok ? ids_map[row] : -1, k, lane);
+    }
   }
   if (w > 0) {
     mv[w][lane] = bv;
@@ -736,20 +807,31 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(const float* __restr
 // and so the last bits of a distance, depend on S -- i.e. on the index size only)
 static int scan_slices(int n) { return n < 65536 ? 4 : (n < 262144 ? 2 : 1); }
 
-template <int QB, int S>
+// M: the filtered instantiations (RowMask mk; the unmasked ones never read it)
+template <bool M, int QB, int S>
 static void launch_scan(dim3 grid, size_t lds, hipStream_t st, const float* xt, int cap, int d, int rb, int re,
-                        int ntiles, const float* q, int nq, int k, float* od, int* oi, const int* ids) {
-  hipLaunchKernelGGL((l2_scan_kernel<QB, S>), grid, dim3(ST), lds, st, xt, cap, d, rb, re, ntiles, q, nq, k, od, oi,
-                     ids);
+                        int ntiles, const float* q, int nq, int k, float* od, int* oi, const int* ids,
+                        const RowMask& mk) {
+  hipLaunchKernelGGL((l2_scan_kernel<QB, S, M>), grid, dim3(ST), lds, st, xt, cap, d, rb, re, ntiles, q, nq, k, od, oi,
+                     ids, mk);
 }
 
-template <int QB>
+template <bool M, int QB>
 static void launch_scan_s(int S, dim3 grid, hipStream_t st, const float* xt, int cap, int d, int rb, int re,
-                          int ntiles, const float* q, int nq, int k, float* od, int* oi, const int* ids) {
+                          int ntiles, const float* q, int nq, int k, float* od, int* oi, const int* ids,
+                          const RowMask& mk) {
   const size_t lds = (size_t)QB * DCH * 4 + (size_t)(S - 1) * (4 / S) * QB * 64 * 4;
-  if (S == 4) launch_scan<QB, 4>(grid, lds, st, xt, cap, d, rb, re, ntiles, q, nq, k, od, oi, ids);
-  else if (S == 2) launch_scan<QB, 2>(grid, lds, st, xt, cap, d, rb, re, ntiles, q, nq, k, od, oi, ids);
-  else launch_scan<QB, 1>(grid, lds, st, xt, cap, d, rb, re, ntiles, q, nq, k, od, oi, ids);
+  if (S == 4) launch_scan<M, QB, 4>(grid, lds, st, xt, cap, d, rb, re, ntiles, q, nq, k, od, oi, ids, mk);
+  else if (S == 2) launch_scan<M, QB, 2>(grid, lds, st, xt, cap, d, rb, re, ntiles, q, nq, k, od, oi, ids, mk);
+  else launch_scan<M, QB, 1>(grid, lds, st, xt, cap, d, rb, re, ntiles, q, nq, k, od, oi, ids, mk);
+}
+
+template <bool M, int QT, int RT>
+static void launch_mfma(dim3 grid, size_t lds, hipStream_t st, const float* xt, int cap, int d, int rb, int re,
+                        int ntiles, const float* q, int nq, int k, float* od, int* oi, const int* ids,
+                        const RowMask& mk) {
+  hipLaunchKernelGGL((l2_mfma_kernel<QT, RT, M>), grid, dim3(ST), lds, st, xt, cap, d, rb, re, ntiles, q, nq, k, od, oi,
+                     ids, mk);
 }
 
 // the MFMA path (batched queries, k <= 8, d % 32 == 0) for nq >= this
@@ -784,19 +866,18 @@ RAGK_API int ragk_l2_search_groups(int row_begin, int row_end, int nq, int k, in
   return max(1, min(ntiles, max(1, 2048 / qgroups)));
 }
 
-// Exact top-k (k <= 64) over rows [row_begin, row_end) of xt[d][cap]; part_d / part_i hold
-// nq * ragk_l2_scan_groups(...) * k entries; results -> out_d / out_i [nq][k].
-RAGK_API int ragk_l2_search(const float* xt, int cap, int d, int row_begin, int row_end, const float* q, int nq,
-                            int k, const int* ids_map, float* part_d, int* part_i, float* out_d,
-                            long long* out_i, hipStream_t st) {
+template <bool M>
+static int l2_search_impl(const float* xt, int cap, int d, int row_begin, int row_end, const float* q, int nq, int k,
+                          const int* ids_map, const RowMask& mk, float* part_d, int* part_i, float* out_d,
+                          long long* out_i, hipStream_t st) {
   if (nq <= 0) return 0;
   if (k < 1 || k > 64 || d < 1 || cap < 1 || row_end > cap) return (int)hipErrorInvalidValue;
   if (use_mfma(nq, k, d)) {
     static bool attr = false;
     if (!attr) {
       hipError_t e = hipSuccess;
-      const void* fns[4] = {(const void*)l2_mfma_kernel<1, 1>, (const void*)l2_mfma_kernel<1, 4>,
-                            (const void*)l2_mfma_kernel<2, 1>, (const void*)l2_mfma_kernel<2, 4>};
+      const void* fns[4] = {(const void*)l2_mfma_kernel<1, 1, M>, (const void*)l2_mfma_kernel<1, 4, M>,
+                            (const void*)l2_mfma_kernel<2, 1, M>, (const void*)l2_mfma_kernel<2, 4, M>};
       for (int i = 0; i < 4 && e == hipSuccess; ++i)
         e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)mfma_lds(MQ_DMAX, 1 + i / 2));
       if (e != hipSuccess) return (int)e;
@@ -809,8 +890,8 @@ RAGK_API int ragk_l2_search(const float* xt, int cap, int d, int row_begin, int 
     const int QT = nq >= 32 ? 2 : 1;
     const dim3 grid(G, (nq + 16 * QT - 1) / (16 * QT));
     const size_t lds = mfma_lds(d, QT);
-#define RAGK_MQ(Q, R) hipLaunchKernelGGL((l2_mfma_kernel<Q, R>), grid, dim3(ST), lds, st, xt, cap, d, row_begin, row_end, \
-                                         ntiles, q, nq, k, part_d, part_i, ids_map)
+#define RAGK_MQ(Q, R) launch_mfma<M, Q, R>(grid, lds, st, xt, cap, d, row_begin, row_end, ntiles, q, nq, k, part_d, \
+                                           part_i, ids_map, mk)
     if (QT == 2) {
       if (RT == 4) RAGK_MQ(2, 4); else RAGK_MQ(2, 1);
     } else {
@@ -830,15 +911,47 @@ RAGK_API int ragk_l2_search(const float* xt, int cap, int d, int row_begin, int 
   // the last group of the y-dimension may be partial (handled in-kernel)
   const int QB = nq >= 16 ? 16 : (nq >= 8 ? 8 : (nq >= 4 ? 4 : (nq >= 2 ? 2 : 1)));
   const dim3 grid(G, (nq + QB - 1) / QB);
-  if (QB == 16) launch_scan_s<16>(S, grid, st, xt, cap, d, row_begin, row_end, ntiles, q, nq, k, part_d, part_i, ids_map);
-  else if (QB == 8) launch_scan_s<8>(S, grid, st, xt, cap, d, row_begin, row_end, ntiles, q, nq, k, part_d, part_i, ids_map);
-  else if (QB == 4) launch_scan_s<4>(S, grid, st, xt, cap, d, row_begin, row_end, ntiles, q, nq, k, part_d, part_i, ids_map);
-  else if (QB == 2) launch_scan_s<2>(S, grid, st, xt, cap, d, row_begin, row_end, ntiles, q, nq, k, part_d, part_i, ids_map);
-  else launch_scan_s<1>(S, grid, st, xt, cap, d, row_begin, row_end, ntiles, q, nq, k, part_d, part_i, ids_map);
+#define RAGK_SC(B) launch_scan_s<M, B>(S, grid, st, xt, cap, d, row_begin, row_end, ntiles, q, nq, k, part_d, part_i, \
+                                       ids_map, mk)
+  if (QB == 16) RAGK_SC(16);
+  else if (QB == 8) RAGK_SC(8);
+  else if (QB == 4) RAGK_SC(4);
+  else if (QB == 2) RAGK_SC(2);
+  else RAGK_SC(1);
+#undef RAGK_SC
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(topk_lists_merge_kernel, dim3(nq), dim3(MW * 64), 0, st, part_d, part_i, G, k, out_d, out_i);
   return (int)hipGetLastError();
+}
+
+// Exact top-k (k <= 64) over rows [row_begin, row_end) of xt[d][cap]; part_d / part_i hold
+// nq * ragk_l2_search_groups(...) * k entries; results -> out_d / out_i [nq][k].
+RAGK_API int ragk_l2_search(const float* xt, int cap, int d, int row_begin, int row_end, const float* q, int nq,
+                            int k, const int* ids_map, float* part_d, int* part_i, float* out_d,
+                            long long* out_i, hipStream_t st) {
+  return l2_search_impl<false>(xt, cap, d, row_begin, row_end, q, nq, k, ids_map, RowMask{}, part_d, part_i, out_d,
+                               out_i, st);
+}
+
+// a bitmap row must hold mask_bits bits; the caller (who owns the tensors) checks that every qmask
+// entry is in [-1, n_masks)
+static bool mask_args_ok(const unsigned* masks, int mask_stride_words, int mask_bits, const int* qmask) {
+  return qmask && mask_bits >= 0 && mask_stride_words >= 0 && (long long)mask_stride_words * 32 >= mask_bits &&
+         (masks || mask_bits == 0);
+}
+
+// As ragk_l2_search over the rows each query's bitmap allows (RowMask above): masks
+// [n_masks][mask_stride_words] uint32, qmask int32 [nq] (mask row, or -1 = unfiltered). Same partial
+// list sizing (ragk_l2_search_groups); missing results are (-1, FLT_MAX).
+RAGK_API int ragk_l2_search_masked(const float* xt, int cap, int d, int row_begin, int row_end, const float* q,
+                                   int nq, int k, const int* ids_map, const unsigned* masks, int mask_stride_words,
+                                   int mask_bits, const int* qmask, float* part_d, int* part_i, float* out_d,
+                                   long long* out_i, hipStream_t st) {
+  if (nq <= 0) return 0;
+  if (!mask_args_ok(masks, mask_stride_words, mask_bits, qmask)) return (int)hipErrorInvalidValue;
+  return l2_search_impl<true>(xt, cap, d, row_begin, row_end, q, nq, k, ids_map,
+                              RowMask{masks, qmask, mask_stride_words, mask_bits}, part_d, part_i, out_d, out_i, st);
 }
 
 // IVF: part buffers hold nq * nprobe * k entries; results -> out [nq][k]
@@ -847,8 +960,25 @@ RAGK_API int ragk_ivf_search(const float* xt, int cap, int d, const float* q, in
                              int* part_i, float* out_d, long long* out_i, hipStream_t st) {
   if (nq <= 0) return 0;
   if (d > IVF_DMAX || k < 1 || k > 64 || nprobe < 1 || cap < 1) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(ivf_scan_kernel, dim3(nprobe, nq), dim3(ST), 0, st, xt, cap, d, q, probes, nprobe, offsets, ends,
-                     ids_map, k, part_d, part_i);
+  hipLaunchKernelGGL(ivf_scan_kernel<false>, dim3(nprobe, nq), dim3(ST), 0, st, xt, cap, d, q, probes, nprobe, offsets,
+                     ends, ids_map, k, part_d, part_i, RowMask{});
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(topk_lists_merge_kernel, dim3(nq), dim3(MW * 64), 0, st, part_d, part_i, nprobe, k, out_d,
+                     out_i);
+  return (int)hipGetLastError();
+}
+
+// As ragk_ivf_search over the ids each query's bitmap allows (looked up by ids_map[row])
+RAGK_API int ragk_ivf_search_masked(const float* xt, int cap, int d, const float* q, int nq, const int* probes,
+                                    int nprobe, const int* offsets, const int* ends, const int* ids_map, int k,
+                                    const unsigned* masks, int mask_stride_words, int mask_bits, const int* qmask,
+                                    float* part_d, int* part_i, float* out_d, long long* out_i, hipStream_t st) {
+  if (nq <= 0) return 0;
+  if (d > IVF_DMAX || k < 1 || k > 64 || nprobe < 1 || cap < 1) return (int)hipErrorInvalidValue;
+  if (!mask_args_ok(masks, mask_stride_words, mask_bits, qmask)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(ivf_scan_kernel<true>, dim3(nprobe, nq), dim3(ST), 0, st, xt, cap, d, q, probes, nprobe, offsets,
+                     ends, ids_map, k, part_d, part_i, RowMask{masks, qmask, mask_stride_words, mask_bits});
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(topk_lists_merge_kernel, dim3(nq), dim3(MW * 64), 0, st, part_d, part_i, nprobe, k, out_d,

@@ -18,6 +18,73 @@ import torch
 FLT_MAX = float(np.finfo(np.float32).max)
 
 
+# ---------------------------------------------------------------- filtered search: id bitmaps
+# masks: uint32 [n_masks, words], bit (id & 31) of word (id >> 5) set = the id may be returned; an id
+# past 32 * words is not allowed. qmask: int [nq], the bitmap row of each query, -1 = unfiltered.
+def pack_masks(allowed) -> np.ndarray:
+    """bool [n_masks, n_ids] -> uint32 [n_masks, ceil(n_ids / 32)] bitmap rows."""
+    a = np.atleast_2d(np.asarray(allowed, dtype=bool))
+    pad = (-a.shape[1]) % 32
+    if pad:
+        a = np.concatenate([a, np.zeros((a.shape[0], pad), bool)], axis=1)
+    return np.ascontiguousarray(np.packbits(a, axis=1, bitorder="little")).view(np.uint32).reshape(a.shape[0], -1)
+
+
+def masks_host(masks) -> np.ndarray:
+    """Bitmap rows (numpy or torch, int32 or uint32) as a uint32 numpy array [n_masks, words]."""
+    if isinstance(masks, torch.Tensor):
+        masks = masks.detach().cpu().view(torch.int32).numpy()
+    m = np.ascontiguousarray(masks)
+    if m.dtype != np.uint32:
+        if m.dtype != np.int32:
+            raise ValueError("masks must be uint32 / int32 words")
+        m = m.view(np.uint32)
+    if m.ndim != 2:
+        raise ValueError("masks must be [n_masks, words]")
+    return m
+
+
+def masks_device(masks, device) -> torch.Tensor:
+    """Bitmap rows as the int32 device tensor the kernels take (a device tensor passes through)."""
+    if isinstance(masks, torch.Tensor) and masks.is_cuda:
+        return masks
+    return torch.from_numpy(masks_host(masks).view(np.int32)).to(device)
+
+
+def qmask_host(qmask, nq, n_masks) -> np.ndarray:
+    qm = np.asarray(qmask.cpu() if isinstance(qmask, torch.Tensor) else qmask).astype(np.int64).reshape(-1)
+    if qm.shape[0] != nq or (nq and (qm.min() < -1 or qm.max() >= n_masks)):
+        raise ValueError("qmask: one entry in [-1, n_masks) per query")
+    return qm
+
+
+def mask_allowed(masks, qmask, ids) -> np.ndarray:
+    """bool [nq, len(ids)]: may query j return ids[i]? (host form of the kernels' test)"""
+    m = masks_host(masks)
+    ids = np.asarray(ids, dtype=np.int64)
+    if qmask is None or masks is None:
+        raise ValueError("masks and qmask go together")
+    qm = qmask_host(qmask, len(qmask), m.shape[0])
+    inb = (ids >= 0) & (ids < 32 * m.shape[1])
+    word, bit = np.where(inb, ids >> 5, 0), (ids & 31).astype(np.uint32)
+    out = np.ones((qm.shape[0], ids.shape[0]), dtype=bool)
+    for r in np.unique(qm[qm >= 0]):
+        row = (((m[r][word] >> bit) & 1).astype(bool) & inb) if m.shape[1] else np.zeros(ids.shape[0], bool)
+        out[qm == r] = row
+    return out
+
+
+COMPACT_PIECE_FLOATS = 4 << 20  # FlatL2Index.compact on the device moves rows in pieces of <= 16 MB
+
+
+def check_keep(keep, ntotal) -> np.ndarray:
+    """compact(keep): the ids to keep, strictly ascending, within [0, ntotal)."""
+    keep = np.asarray(keep, dtype=np.int64).reshape(-1)
+    if len(keep) and (keep[0] < 0 or keep[-1] >= ntotal or bool((np.diff(keep) <= 0).any())):
+        raise ValueError("keep must be strictly ascending ids within [0, ntotal)")
+    return keep
+
+
 class FlatL2Index:
     def __init__(self, d: int, device="cpu", capacity: int = 1024):
         self.d = int(d)
@@ -68,9 +135,30 @@ class FlatL2Index:
         with self._lock:
             self.ntotal = 0
 
+    def compact(self, keep):
+        """Drop every vector whose id is not in `keep` (sorted ids): afterwards the index equals a fresh one
+        to which the kept vectors were added in their original order (new id = rank among the kept).
+        In place: a kept row only ever moves down, so pieces of rows are gathered (l2_gather) and written
+        back (l2_append) in ascending order -- one bounded row-major piece is the only temporary."""
+        with self._lock:
+            keep = check_keep(keep, self.ntotal)
+            m = len(keep)
+            if m == self.ntotal:
+                return
+            if self._n is not None:
+                step = max(1, COMPACT_PIECE_FLOATS // self.d)
+                idx = torch.from_numpy(keep.astype(np.int32)).to(self.device)
+                for i in range(0, m, step):
+                    # stream order: the piece is read completely before its (lower) slots are written
+                    self._n.l2_append(self._xt, self._cap, i, self._n.l2_gather(self._xt, self._cap, idx[i:i + step]))
+            elif m:
+                self._xb[:m] = self._xb[torch.from_numpy(keep)]
+            self.ntotal = m
+
     # ---------------------------------------------------------------- query
-    def search(self, q, k):
-        """q: [nq, d] -> (D fp32 [nq,k], I int64 [nq,k]) on the host."""
+    def search(self, q, k, masks=None, qmask=None):
+        """q: [nq, d] -> (D fp32 [nq,k], I int64 [nq,k]) on the host. masks / qmask: filtered search
+        (id bitmaps, see pack_masks) -- query j only returns ids allowed by bitmap row qmask[j]."""
         q = torch.as_tensor(q).reshape(-1, self.d).float().contiguous()
         nq = q.shape[0]
         if nq == 0:
@@ -79,16 +167,20 @@ class FlatL2Index:
             if self._n is not None:
                 if k > 64:
                     raise ValueError("k <= 64 on the GPU path")
-                D, I = self._n.l2_search(self._xt, self._cap, self.ntotal, q.to(self.device), k)
+                D, I = self.search_device(q.to(self.device), k, masks, qmask)
                 return D.cpu(), I.cpu()
-            return self._cpu_search(q, k)
+            return self._cpu_search(q, k, masks, qmask)
 
-    def search_device(self, q, k):
-        """GPU-only: q on device -> (D, I) on device (no host sync)."""
+    def search_device(self, q, k, masks=None, qmask=None):
+        """GPU-only: q on device -> (D, I) on device (no host sync without a filter)."""
         with self._lock:
-            return self._n.l2_search(self._xt, self._cap, self.ntotal, q, k)
+            if masks is None and qmask is None:
+                return self._n.l2_search(self._xt, self._cap, self.ntotal, q, k)
+            md = masks_device(masks, self.device)
+            qm = qmask if isinstance(qmask, torch.Tensor) else torch.from_numpy(np.asarray(qmask, dtype=np.int32))
+            return self._n.l2_search(self._xt, self._cap, self.ntotal, q, k, masks=md, qmask=qm.int().contiguous())
 
-    def _cpu_search(self, q, k):
+    def _cpu_search(self, q, k, masks=None, qmask=None):
         n = self.ntotal
         D = torch.full((q.shape[0], k), FLT_MAX)
         I = torch.full((q.shape[0], k), -1, dtype=torch.int64)
@@ -99,6 +191,14 @@ class FlatL2Index:
         d = (q * q).sum(1, keepdim=True) + (xb * xb).sum(1)[None, :] - 2.0 * (q @ xb.t())
         d = d.clamp_min_(0.0)
         kk = min(k, n)
+        if masks is not None or qmask is not None:
+            # rows a query may not return sort last (inf; real distances are finite) and become padding
+            d[~torch.from_numpy(mask_allowed(masks, qmask, np.arange(n)))] = float("inf")
+            dv, di = torch.sort(d, dim=1, stable=True)
+            live = dv[:, :kk] != float("inf")
+            D[:, :kk] = torch.where(live, dv[:, :kk], D[:, :kk])
+            I[:, :kk] = torch.where(live, di[:, :kk], I[:, :kk])
+            return D, I
         dv, di = torch.sort(d, dim=1, stable=True)
         D[:, :kk] = dv[:, :kk]
         I[:, :kk] = di[:, :kk]

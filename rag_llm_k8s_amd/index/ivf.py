@@ -29,7 +29,7 @@ import threading
 import numpy as np
 import torch
 
-from .flat import FLT_MAX
+from .flat import FLT_MAX, check_keep, mask_allowed, masks_device
 
 MAX_POINTS_PER_CENTROID = 256  # faiss ClusteringParameters default
 
@@ -225,7 +225,8 @@ class IVFFlatIndex:
             self.ntotal += len(x)
 
     # ------------------------------------------------------------------ query
-    def search(self, q, k):
+    def search(self, q, k, masks=None, qmask=None):
+        """masks / qmask: filtered search (id bitmaps, index/flat.pack_masks), looked up by original id."""
         q = torch.as_tensor(q).reshape(-1, self.d).float().contiguous()
         nq = q.shape[0]
         with self._lock:
@@ -237,18 +238,25 @@ class IVFFlatIndex:
 
                 qd = q.to(self.device, non_blocking=True)
                 pr = self._coarse_device(qd, nprobe)  # stays on the device: one host sync per search
+                if masks is not None or qmask is not None:
+                    qm = qmask if isinstance(qmask, torch.Tensor) else torch.from_numpy(np.asarray(qmask, np.int32))
+                    D, I = native.ivf_search(self._xt, self._cap, qd, pr, self._start_dev, self._ids_dev, k,
+                                             ends=self._end_dev, masks=masks_device(masks, self.device),
+                                             qmask=qm.int().contiguous())
+                    return D.cpu(), I.cpu()
                 D, I = native.ivf_search(self._xt, self._cap, qd, pr, self._start_dev, self._ids_dev, k,
                                          max_list=int(self._size.max()), ends=self._end_dev)
                 return D.cpu(), I.cpu()
             pr = probes(q.to(self.centroids.device), self.centroids, self._cnorm, nprobe).cpu()
-            return self._search_host(q, pr, k)
+            return self._search_host(q, pr, k, masks, qmask)
 
     def _coarse_device(self, qd, nprobe):
         """Top-nprobe centroids per query as int32 [nq, nprobe] on the device."""
         return probes(qd, self.centroids, self._cnorm, nprobe).int().contiguous()
 
-    def _search_host(self, q, probes, k):
+    def _search_host(self, q, probes, k, masks=None, qmask=None):
         nq = q.shape[0]
+        masked = masks is not None or qmask is not None
         D = torch.full((nq, k), FLT_MAX)
         I = torch.full((nq, k), -1, dtype=torch.int64)
         lists, idl = self.lists, self.ids
@@ -258,12 +266,41 @@ class IVFFlatIndex:
                 continue
             x = torch.from_numpy(np.concatenate([lists[p] for p in ls]))
             ids = torch.from_numpy(np.concatenate([idl[p] for p in ls]))
+            if masked:  # only the ids this query's bitmap allows
+                al = torch.from_numpy(mask_allowed(masks, np.asarray(qmask).reshape(-1)[qi:qi + 1], ids.numpy())[0])
+                x, ids = x[al], ids[al]
             d = ((x - q[qi][None]) ** 2).sum(1)
             order = torch.argsort(d, stable=True)
             kk = min(k, len(order))
             D[qi, :kk] = d[order[:kk]]
             I[qi, :kk] = ids[order[:kk]]
         return D, I
+
+    def compact(self, keep):
+        """Drop every vector whose id is not in `keep` (sorted ids); new id = rank among the kept. Centroids
+        and list assignment stay: the index equals one with these centroids to which the kept vectors were
+        added in their original order. The device store is rebuilt from the host lists."""
+        with self._lock:
+            keep = check_keep(keep, self.ntotal)
+            if len(keep) == self.ntotal:
+                return
+            lists, ids = self.lists, self.ids
+            for li in range(len(lists)):
+                sel = np.isin(ids[li], keep, assume_unique=True)
+                x, i = lists[li][sel], np.searchsorted(keep, ids[li][sel]).astype(np.int64)
+                self._xchunks[li] = [x] if len(i) else []
+                self._ichunks[li] = [i] if len(i) else []
+            self.ntotal = len(keep)
+            self._reset_store()
+            if self.device.type == "cuda" and self.ntotal:
+                self._load_device()
+
+    def _load_device(self):
+        """Device store from the host lists (list order = the order the rows were added in)."""
+        lists, ids = self.lists, self.ids
+        a = np.concatenate([np.full(len(i), li, np.int64) for li, i in enumerate(ids)])
+        x = torch.from_numpy(np.concatenate(lists)).to(self.device)
+        self._append_device(x, a, np.concatenate(ids))
 
     # ------------------------------------------------------------------ host lists
     def _compact(self, li):

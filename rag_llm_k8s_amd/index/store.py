@@ -12,7 +12,13 @@ Reference behaviour and its fixes:
   * faiss label -1 mapped to metadata[-1] (last chunk)     -> -1 results are dropped, making the
     "No relevant information found" branch reachable;
   * startup re-ingest duplicates chunks                    -> idempotent by (filename, chunk_id)
-    unless reingest_append=True (legacy behaviour).
+    unless reingest_append=True (legacy behaviour);
+  * a document can never be removed, replaced or excluded  -> delete(filename) / add(replace=True) and
+    search(filters=...). A delete clears the chunks' bits in a LIVE BITMAP (a tombstone): the very next
+    search runs masked (the kernels' top-k over the rows a per-query bitmap allows) and no longer sees
+    them. The next snapshot first COMPACTS (index.compact + metadata filtered, bitmap reset), so the
+    files on disk are always plain reference-format files of exactly the live chunks and the resident
+    ids stay aligned with them. A filename filter is one more bitmap row, ANDed with the live one.
 """
 from __future__ import annotations
 
@@ -23,9 +29,9 @@ import time
 
 import numpy as np
 
-from ..utils import faults
+from ..utils import faults, metrics
 from .faiss_io import load_metadata, read_index, save_metadata
-from .flat import FlatL2Index
+from .flat import FlatL2Index, pack_masks
 
 log = logging.getLogger(__name__)
 
@@ -58,6 +64,13 @@ class DocumentStore:
         self._writing = 0  # snapshot writes in flight (their file replacements are not "other writers")
         self._persister = None
         self._persist_error = None
+        self._reset_live()
+
+    def _reset_live(self):
+        """No tombstones: every metadata entry is live (state after a load or a compaction)."""
+        self._live = None  # bool [len(metadata)] once a chunk was deleted; None = all live
+        self._dead = 0     # tombstoned chunks still in the index
+        self._by_file = None  # filename -> ids of its chunks (cache; rebuilt after any change)
 
     def _new_index(self):
         if self.sharded:
@@ -100,6 +113,7 @@ class DocumentStore:
         self.index = self._new_index()
         self.metadata = []
         self._keys = set()
+        self._reset_live()
         self.recovered = tag
 
     def _disk_mtimes(self):
@@ -122,6 +136,7 @@ class DocumentStore:
             idx.load_local(r["xb"] if r["ntotal"] else None, len(meta))
             self.index, self.metadata = idx, list(meta)
             self._keys = {(m.get("filename"), m.get("chunk_id")) for m in self.metadata if isinstance(m, dict)}
+            self._reset_live()
             self._mtimes = self._disk_mtimes()
             return
         if len(meta) != r["ntotal"]:
@@ -138,6 +153,7 @@ class DocumentStore:
         self.index = idx
         self.metadata = list(meta)
         self._keys = {(m.get("filename"), m.get("chunk_id")) for m in self.metadata if isinstance(m, dict)}
+        self._reset_live()
         self._mtimes = self._disk_mtimes()
 
     def maybe_reload(self):
@@ -161,8 +177,24 @@ class DocumentStore:
                 log.warning("index on disk changed but is unreadable (%s); keeping the resident copy", e)
                 self._mtimes = m
 
+    def _compact(self):
+        """Drop the tombstoned chunks from the index and the metadata (caller holds _wlock): ids are
+        renumbered by rank among the live ones, on both sides, and the live bitmap is reset."""
+        if not self._dead:
+            return
+        keep = np.nonzero(self._live)[0]
+        self.index.compact(keep)
+        self.metadata = [self.metadata[i] for i in keep.tolist()]  # a new list: searches in flight keep theirs
+        self._reset_live()
+        metrics.inc("index_compactions")
+        metrics.set_gauge("index_tombstones", 0)
+        metrics.set_gauge("index", self.index.ntotal)
+        log.info("Index compacted. Total vectors: %d", self.index.ntotal)
+
     def _snapshot(self):
-        """(index writer, metadata copy) of the current state; caller holds _wlock."""
+        """(index writer, metadata copy) of the current state, compacted first, so the files only ever
+        hold live chunks; caller holds _wlock."""
+        self._compact()
         return self.index.snapshot_writer(), list(self.metadata)
 
     def _write(self, writer, meta):
@@ -237,12 +269,19 @@ class DocumentStore:
                 self._write(writer, meta)
 
     # ------------------------------------------------------------------ writes
-    def add(self, vectors, metadata, dedupe=True, persist=True):
-        """Append vectors + metadata (reference update_index). Returns number added."""
+    def add(self, vectors, metadata, dedupe=True, persist=True, replace=False):
+        """Append vectors + metadata (reference update_index). Returns number added.
+        replace: first delete every chunk of the documents named in `metadata`, under the same lock -- no
+        search sees neither or both versions of a document."""
         vecs = np.asarray(vectors.cpu() if hasattr(vectors, "cpu") else vectors, dtype=np.float32)
         if vecs.ndim == 1:
             vecs = vecs.reshape(1, -1)
+        if replace and self.sharded:
+            raise ValueError(self.SHARDED_REFUSAL % "replace")
         with self._wlock:
+            if replace:
+                for fn in dict.fromkeys(m["filename"] for m in metadata):
+                    self.delete(fn, persist=False)
             keep = list(range(len(metadata)))
             if dedupe:
                 keep = [i for i, m in enumerate(metadata) if (m["filename"], m["chunk_id"]) not in self._keys]
@@ -253,16 +292,110 @@ class DocumentStore:
                 for i in keep:
                     self.metadata.append(metadata[i])
                     self._keys.add((metadata[i]["filename"], metadata[i]["chunk_id"]))
+                if self._live is not None:
+                    self._live = np.concatenate([self._live, np.ones(len(keep), dtype=bool)])
+                self._by_file = None
+            if keep or (replace and self._dead):
                 if persist:
                     self.persist_async()
             log.info("Index updated. Total vectors: %d, Dimension: %d", self.index.ntotal, self.dim)
             return len(keep)
 
+    SHARDED_REFUSAL = ("document %s is not supported on a row-sharded index (INDEX_SHARDED): the shards would "
+                       "have to be re-balanced and the filter broadcast to every rank")
+
+    def delete(self, filename, persist=True):
+        """Remove every chunk of a document. Returns the number of chunks removed (0: unknown document).
+        The chunks' bits are cleared in the live bitmap (they are gone for the very next search), their
+        (filename, chunk_id) keys dropped (the document can be uploaded again), and a snapshot -- which
+        compacts index and metadata first -- is scheduled."""
+        if self.sharded:
+            raise ValueError(self.SHARDED_REFUSAL % "delete")
+        with self._wlock:
+            ids = self._file_ids().get(filename)
+            if ids is not None and self._live is not None:
+                ids = ids[self._live[ids]]
+            if ids is None or not len(ids):
+                return 0
+            if self._live is None:
+                self._live = np.ones(len(self.metadata), dtype=bool)
+            self._live[ids] = False
+            self._dead += len(ids)
+            for i in ids.tolist():
+                self._keys.discard((filename, self.metadata[i].get("chunk_id")))
+            metrics.inc("index_chunks_deleted", len(ids))
+            metrics.set_gauge("index_tombstones", self._dead)
+            log.info("Deleted %d chunks of %s. Live vectors: %d", len(ids), filename, self.index.ntotal - self._dead)
+            if persist:
+                self.persist_async()
+            return int(len(ids))
+
     # ------------------------------------------------------------------ reads
-    def search(self, qvecs, k):
-        """Batched search -> list (per query) of [(metadata, squared_l2)] ascending, -1 dropped."""
+    def _file_ids(self):
+        """filename -> int64 ids of its chunks, tombstoned ones included (caller holds _wlock)."""
+        if self._by_file is None:
+            by = {}
+            for i, m in enumerate(self.metadata):
+                if isinstance(m, dict):
+                    by.setdefault(m.get("filename"), []).append(i)
+            self._by_file = {fn: np.asarray(v, dtype=np.int64) for fn, v in by.items()}
+        return self._by_file
+
+    def documents(self):
+        """[{"filename", "chunks"}] of the live chunks, in first-seen order."""
+        with self._wlock:
+            out = []
+            for fn, ids in self._file_ids().items():
+                n = int(len(ids) if self._live is None else self._live[ids].sum())
+                if n:
+                    out.append({"filename": fn, "chunks": n})
+            return out
+
+    def _filter_masks(self, filters, nq):
+        """Per-query filename filters -> (bitmap rows uint32 [n_rows, words], qmask int32 [nq]) for one masked
+        search, or (None, None) when nothing restricts it. One row per DISTINCT filter of the batch, each
+        ANDed with the live bitmap; unfiltered queries use the live row while tombstones exist, else -1.
+        Caller holds _wlock."""
+        filters = list(filters) if filters is not None else [None] * nq
+        if len(filters) != nq:
+            raise ValueError("filters: one entry (None or filenames) per query")
+        if self._dead == 0 and all(f is None for f in filters):
+            return None, None
+        n = len(self.metadata)
+        live = self._live if self._live is not None else np.ones(n, dtype=bool)
+        rows, row_of, qmask = [], {}, np.full(nq, -1, dtype=np.int32)
+        for j, f in enumerate(filters):
+            if f is None and self._dead == 0:
+                continue
+            key = None if f is None else frozenset([f] if isinstance(f, str) else f)
+            if key not in row_of:
+                if key is None:
+                    al = live
+                else:
+                    al = np.zeros(n, dtype=bool)
+                    for fn in key:
+                        ids = self._file_ids().get(fn)
+                        if ids is not None:
+                            al[ids] = True
+                    al &= live
+                row_of[key] = len(rows)
+                rows.append(al)
+            qmask[j] = row_of[key]
+        return pack_masks(np.stack(rows)), qmask
+
+    def search(self, qvecs, k, filters=None):
+        """Batched search -> list (per query) of [(metadata, squared_l2)] ascending, -1 dropped.
+        filters: per query None or a collection of filenames the results must come from (a filter naming
+        no known document yields no results for that query)."""
+        if self.sharded and filters is not None and any(f is not None for f in filters):
+            raise ValueError(self.SHARDED_REFUSAL % "filtering")
         with self._wlock:  # consistent (index, metadata) pair: an append cannot land in between
-            D, I = self.index.search(qvecs, k)
+            nq = int(np.prod(np.shape(qvecs))) // self.dim if (filters is not None or self._dead) else 0
+            masks, qmask = self._filter_masks(filters, nq) if nq else (None, None)
+            if masks is None:
+                D, I = self.index.search(qvecs, k)
+            else:
+                D, I = self.index.search(qvecs, k, masks=masks, qmask=qmask)
             meta = self.metadata
             n = len(meta)
         out = []
@@ -275,5 +408,11 @@ class DocumentStore:
         return out
 
     def info(self):
-        return {"total_vectors": int(self.index.ntotal), "dimension": int(self.dim),
-                "total_chunks": len(self.metadata), "sample_chunks": self.metadata[:5] if self.metadata else []}
+        with self._wlock:
+            if not self._dead:
+                return {"total_vectors": int(self.index.ntotal), "dimension": int(self.dim),
+                        "total_chunks": len(self.metadata),
+                        "sample_chunks": self.metadata[:5] if self.metadata else []}
+            live = [self.metadata[i] for i in np.nonzero(self._live)[0][:5].tolist()]  # tombstones not counted
+            return {"total_vectors": int(self.index.ntotal) - self._dead, "dimension": int(self.dim),
+                    "total_chunks": len(self.metadata) - self._dead, "sample_chunks": live}

@@ -86,6 +86,8 @@ _SIGS = {
     "ragk_l2_search_set_mfma_min_nq": [I],
     "ragk_l2_search": [P, I, I, I, I, P, I, I, P, P, P, P, P, S],
     "ragk_ivf_search": [P, I, I, P, I, P, I, P, P, P, I, P, P, P, P, S],
+    "ragk_l2_search_masked": [P, I, I, I, I, P, I, I, P, P, I, I, P, P, P, P, P, S],
+    "ragk_ivf_search_masked": [P, I, I, P, I, P, I, P, P, P, I, P, I, I, P, P, P, P, P, S],
     "ragk_kmeans_assign": [P, I, I, P, P, I, P, P, P, S],
     "ragk_l2_scatter": [P, I, I, P, P, I, S],
     "ragk_l2_append": [P, I, I, I, P, I, S],

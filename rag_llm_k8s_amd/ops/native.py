@@ -1295,13 +1295,38 @@ def _search_partials(n_entries, device):
     return ws[:n_entries].view(torch.float32), ws[n_entries:2 * n_entries]
 
 
-def l2_search(xt, cap, n, q, k, row_begin=0, ids_map=None):
+def _mask_args(masks, qmask, nq, mask_bits, device):
+    """Host-side checks of a filtered search's bitmaps: masks int32 / uint32 [n_masks, words] on the launch
+    device (bit id & 31 of word id >> 5 set = id allowed), qmask int32 [nq] with every entry in [-1, n_masks)
+    (-1 = unfiltered) -- a host tensor is checked without a device sync and uploaded, a device tensor is
+    checked with one. mask_bits (default 32 * words) ids are covered; ids past it are not allowed.
+    Returns (masks, words, mask_bits, qmask on the device)."""
+    _req(masks is not None and qmask is not None, "masks and qmask go together")
+    _req(masks.is_cuda and masks.device == device and masks.dim() == 2 and masks.is_contiguous()
+         and masks.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)), "masks int32 [n_masks, words]")
+    _req(qmask.dtype == torch.int32 and qmask.dim() == 1 and qmask.numel() == nq and qmask.is_contiguous(),
+         "qmask int32 [nq]")
+    n_masks, words = masks.shape
+    bits = 32 * words if mask_bits is None else int(mask_bits)
+    _req(0 <= bits <= 32 * words, "mask_bits within the bitmap row")
+    if nq:
+        lo, hi = torch.stack(torch.aminmax(qmask)).tolist()  # a device qmask: one sync
+        _req(lo >= -1 and hi < n_masks, "qmask entries in [-1, n_masks)")
+    if not qmask.is_cuda:
+        qmask = qmask.to(device)
+    _req(qmask.device == device, "qmask on the launch device")
+    return masks, words, bits, qmask
+
+
+def l2_search(xt, cap, n, q, k, row_begin=0, ids_map=None, masks=None, qmask=None, mask_bits=None):
     """Exact squared-L2 top-k over rows [row_begin, n) of a column-major store xt[d][cap]
     (csrc/kernels/search.hip: l2_scan with wave-resident running top lists + one list merge; batches
     of >= 16 queries with k <= 8 on the fp32-MFMA distance GEMM, faiss' BLAS form).
     Returns (D fp32 [nq,k], I int64 [nq,k]) with faiss padding semantics (-1, FLT_MAX).
     Host cost per call: one output allocation and two ctypes calls (the partial lists live in a
-    cached workspace), so a single-query search is not dominated by launch overhead."""
+    cached workspace), so a single-query search is not dominated by launch overhead.
+    masks / qmask (see _mask_args): filtered search -- query j only returns ids (ids_map[row], or the
+    row) whose bit is set in bitmap row qmask[j]; fewer than k allowed rows pad with (-1, FLT_MAX)."""
     _req(xt.is_cuda and xt.dtype == torch.float32 and xt.is_contiguous() and xt.dim() == 2, "xt fp32 [d, cap]")
     _req(q.is_cuda and q.dtype == torch.float32 and q.is_contiguous() and q.dim() == 2, "q fp32 [nq, d]")
     d = xt.shape[0]
@@ -1310,6 +1335,8 @@ def l2_search(xt, cap, n, q, k, row_begin=0, ids_map=None):
     _req(1 <= k <= 64, "1 <= k <= 64")
     _req(xt.shape[1] == cap and 0 <= row_begin <= max(row_begin, n) <= cap, "rows within the store")
     _req(ids_map is None or (ids_map.dtype == torch.int32 and ids_map.is_cuda and ids_map.numel() >= n), "ids_map")
+    if masks is not None or qmask is not None:
+        masks, words, bits, qmask = _mask_args(masks, qmask, nq, mask_bits, q.device)
     L = _lib.lib()
     od, oi = _search_out(nq, k, q.device)
     if nq == 0:
@@ -1317,17 +1344,25 @@ def l2_search(xt, cap, n, q, k, row_begin=0, ids_map=None):
     G = L.ragk_l2_search_groups(row_begin, max(n, row_begin), nq, k, d)
     with _search_lock:
         pd, pi = _search_partials(nq * G * k, q.device)
+        if masks is not None:
+            check(L.ragk_l2_search_masked(xt.data_ptr(), cap, d, row_begin, max(n, row_begin), q.data_ptr(), nq, k,
+                                          ptr(ids_map), masks.data_ptr(), words, bits, qmask.data_ptr(),
+                                          pd.data_ptr(), pi.data_ptr(), od.data_ptr(), oi.data_ptr(), stream_ptr()),
+                  "ragk_l2_search_masked")
+            return od, oi
         check(L.ragk_l2_search(xt.data_ptr(), cap, d, row_begin, max(n, row_begin), q.data_ptr(), nq, k,
                                ptr(ids_map), pd.data_ptr(), pi.data_ptr(), od.data_ptr(), oi.data_ptr(), stream_ptr()),
               "ragk_l2_search")
     return od, oi
 
 
-def ivf_search(xt, cap, q, probes, offsets, ids_map, k, max_list=None, ends=None):
+def ivf_search(xt, cap, q, probes, offsets, ids_map, k, max_list=None, ends=None, masks=None, qmask=None,
+               mask_bits=None):
     """IVF-Flat scan of the probed lists (one block per (query, probe), wave-resident top lists,
     then one list merge). probes int32 [nq, nprobe] (device; -1 = no list); list i occupies store rows
     [offsets[i], ends[i]) (ends None: packed lists, offsets has nlist+1 entries); ids_map int32 [cap]
-    original id of every store row. max_list is accepted for API compatibility (unused)."""
+    original id of every store row. max_list is accepted for API compatibility (unused).
+    masks / qmask (see _mask_args): filtered search, the bitmaps indexed by the original id."""
     _req(xt.dtype == torch.float32 and q.dtype == torch.float32 and q.is_contiguous(), "fp32")
     _req(probes.dtype == torch.int32 and offsets.dtype == torch.int32 and ids_map.dtype == torch.int32, "int32")
     _req(probes.is_contiguous() and probes.is_cuda and offsets.is_cuda and ids_map.is_cuda, "device int32")
@@ -1335,11 +1370,20 @@ def ivf_search(xt, cap, q, probes, offsets, ids_map, k, max_list=None, ends=None
     d = xt.shape[0]
     nq, nprobe = probes.shape
     _req(1 <= k <= 64 and d <= 2048 and nprobe >= 1, "k <= 64, d <= 2048")
+    if masks is not None or qmask is not None:
+        masks, words, bits, qmask = _mask_args(masks, qmask, nq, mask_bits, q.device)
     od, oi = _search_out(nq, k, q.device)
     if nq == 0:
         return od, oi
     with _search_lock:
         pd, pi = _search_partials(nq * nprobe * k, q.device)
+        if masks is not None:
+            check(_lib.lib().ragk_ivf_search_masked(xt.data_ptr(), cap, d, q.data_ptr(), nq, probes.data_ptr(), nprobe,
+                                                    offsets.data_ptr(), ptr(ends), ids_map.data_ptr(), k,
+                                                    masks.data_ptr(), words, bits, qmask.data_ptr(), pd.data_ptr(),
+                                                    pi.data_ptr(), od.data_ptr(), oi.data_ptr(), stream_ptr()),
+                  "ragk_ivf_search_masked")
+            return od, oi
         check(_lib.lib().ragk_ivf_search(xt.data_ptr(), cap, d, q.data_ptr(), nq, probes.data_ptr(), nprobe,
                                          offsets.data_ptr(), ptr(ends), ids_map.data_ptr(), k, pd.data_ptr(),
                                          pi.data_ptr(), od.data_ptr(), oi.data_ptr(), stream_ptr()), "ragk_ivf_search")
@@ -1388,5 +1432,21 @@ def l2_append(xt, cap, n0, x):
     _req(x.dtype == torch.float32 and x.is_contiguous() and x.shape[1] == xt.shape[0], "x fp32 [n,d]")
     check(_lib.lib().ragk_l2_append(xt.data_ptr(), cap, xt.shape[0], n0, x.data_ptr(), x.shape[0], stream_ptr()),
           "ragk_l2_append")
+
+
+def l2_gather(xt, cap, idx, out=None):
+    """Rows idx (int32 [n], each in [0, cap); -1 = a zero row) of the column-major store xt[d][cap] ->
+    row-major fp32 [n, d]."""
+    _req(xt.is_cuda and xt.dtype == torch.float32 and xt.is_contiguous() and xt.dim() == 2 and xt.shape[1] == cap,
+         "xt fp32 [d, cap]")
+    _req(idx.dtype == torch.int32 and idx.is_cuda and idx.dim() == 1 and idx.is_contiguous(), "idx int32 [n]")
+    n, d = idx.numel(), xt.shape[0]
+    if out is None:
+        out = torch.empty((n, d), dtype=torch.float32, device=xt.device)
+    _req(out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, d),
+         "out fp32 [n, d]")
+    check(_lib.lib().ragk_l2_gather(xt.data_ptr(), cap, d, idx.data_ptr(), n, out.data_ptr(), stream_ptr()),
+          "ragk_l2_gather")
+    return out
 
 

@@ -9,6 +9,12 @@ Routes (exact request/response/error contract):
                                        | 400 {"error": "No file part" | "No selected file" | "Invalid file format"}
   GET  /index_info   -> {"total_vectors", "dimension", "total_chunks", "sample_chunks"} | 500 {"error"}
 New: GET /healthz (liveness), GET /readyz (weights + index loaded), GET /metrics (Prometheus).
+New (documents can be listed, removed, replaced and filtered on; the reference can only add):
+  POST /generate     optional "filenames": [str, ...] -> the context comes from these documents only
+  POST /upload_pdf?replace=1 (or form field replace=1) -> the document's old chunks are replaced
+  GET  /documents    -> {"documents": [{"filename", "chunks"}]}
+  DELETE /documents/<filename> -> 200 {"message", "chunks_removed"} | 404 {"error"}
+                                | 501 {"error"} on a row-sharded index (INDEX_SHARDED)
 """
 from __future__ import annotations
 
@@ -29,7 +35,11 @@ def create_app(service) -> Flask:
             data = request.json
             user_prompt = data.get("prompt", "")
             debug = bool(data.get("debug", False))
-            out = service.generate(user_prompt, debug=debug)
+            filenames = data.get("filenames")
+            if filenames:
+                out = service.generate(user_prompt, debug=debug, filenames=filenames)
+            else:
+                out = service.generate(user_prompt, debug=debug)
             metrics.inc("requests", route="generate", status="200")
             return jsonify(out)
         except Exception as e:
@@ -48,7 +58,13 @@ def create_app(service) -> Flask:
         if file.filename == "":
             return jsonify({"error": "No selected file"}), 400
         if file and file.filename.endswith(".pdf"):
-            n = service.ingest_pdf_bytes(file.filename, file.read())
+            if str(request.args.get("replace", request.form.get("replace", ""))).lower() in ("1", "true", "yes"):
+                try:
+                    n = service.ingest_pdf_bytes(file.filename, file.read(), replace=True)
+                except ValueError as e:  # row-sharded index
+                    return jsonify({"error": str(e)}), 501
+            else:
+                n = service.ingest_pdf_bytes(file.filename, file.read())
             metrics.inc("requests", route="upload_pdf", status="200")
             return jsonify({"message": f"PDF processed and indexed successfully. {n} chunks created."}), 200
         return jsonify({"error": "Invalid file format"}), 400
@@ -60,6 +76,31 @@ def create_app(service) -> Flask:
         except Exception as e:
             log.error("Error in index_info: %s", str(e), exc_info=True)
             return jsonify({"error": str(e)}), 500
+
+    @app.route("/documents", methods=["GET"])
+    def documents():
+        try:
+            return jsonify({"documents": service.documents()})
+        except Exception as e:
+            log.error("Error in documents: %s", str(e), exc_info=True)
+            return jsonify({"error": str(e)}), 500
+
+    @app.route("/documents/<path:filename>", methods=["DELETE"])
+    def delete_document(filename):
+        try:
+            n = service.delete_document(filename)
+        except ValueError as e:  # row-sharded index: not supported
+            metrics.inc("requests", route="delete_document", status="501")
+            return jsonify({"error": str(e)}), 501
+        except Exception as e:
+            log.error("Error in delete_document: %s", str(e), exc_info=True)
+            metrics.inc("requests", route="delete_document", status="500")
+            return jsonify({"error": str(e)}), 500
+        if n == 0:
+            metrics.inc("requests", route="delete_document", status="404")
+            return jsonify({"error": f"Document not found: {filename}"}), 404
+        metrics.inc("requests", route="delete_document", status="200")
+        return jsonify({"message": f"Document deleted. {n} chunks removed.", "chunks_removed": n}), 200
 
     @app.route("/healthz", methods=["GET"])
     def healthz():

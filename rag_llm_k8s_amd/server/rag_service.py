@@ -302,14 +302,18 @@ class RagService:
         rank 0 retrieves), or by every rank for its row shard (INDEX_SHARDED)."""
         from ..parallel.dp import embed_distributed
 
-        filename, chunks, dedupe, persist = args
+        filename, chunks, dedupe, persist = args[:4]
+        replace = bool(args[4]) if len(args) > 4 else False
         if self.collective or (self.tp_group is not None and not self.loop.is_alive()):
             vecs = embed_distributed(self.embedder, chunks, group=self.tp_group)
         else:  # single process (or a DP replica): never a collective over the default group
             vecs = self.embedder.embed(chunks)
         rank0 = self.tp_group is None or torch.distributed.get_rank(self.tp_group) == 0
         if rank0 or getattr(self.store, "sharded", False):
-            self.store.add(vecs, chunk_metadata(filename, chunks), dedupe=dedupe, persist=persist)
+            if replace:  # old chunks out, new ones in, under one store lock
+                self.store.add(vecs, chunk_metadata(filename, chunks), dedupe=dedupe, persist=persist, replace=True)
+            else:
+                self.store.add(vecs, chunk_metadata(filename, chunks), dedupe=dedupe, persist=persist)
         return len(chunks)
 
     def _job_search(self, args):
@@ -319,7 +323,11 @@ class RagService:
             q = torch.zeros((0, self.store.dim), dtype=torch.float32)
         return self.store.search(q, k)
 
-    def _retrieve_batch(self, prompts):
+    def _retrieve_batch(self, items):
+        """items: (prompt, filter) pairs -- filter None, or the filenames the context must come from. The
+        micro-batcher mixes requests, so one search carries a filter per query (a masked search)."""
+        prompts = [p for p, _ in items]
+        filters = [f for _, f in items]
         tr = Trace("retrieve")
         with tr.span("embed"):
             faults.check("embed_error")
@@ -328,12 +336,26 @@ class RagService:
             self.store.maybe_reload()
             if self.collective and getattr(self.store, "sharded", False):
                 res = self.loop.run_job("search", (q.cpu(), self.cfg.retrieve_k), timeout=self.cfg.request_timeout_s)
+            elif any(f is not None for f in filters):
+                res = self.store.search(q, self.cfg.retrieve_k, filters=filters)
             else:
                 res = self.store.search(q, self.cfg.retrieve_k)
         return [(r, tr.spans) for r in res]
 
-    def retrieve(self, prompt):
-        return self.batcher.submit(prompt)
+    @staticmethod
+    def _filter(filenames):
+        """Request "filenames" -> a store filter: absent / empty = unfiltered."""
+        if not filenames:
+            return None
+        if isinstance(filenames, str):
+            return (filenames,)
+        return tuple(str(f) for f in filenames)
+
+    def retrieve(self, prompt, filenames=None):
+        flt = self._filter(filenames)
+        if flt is not None and getattr(self.store, "sharded", False):  # refused before it joins a batch
+            raise ValueError(self.store.SHARDED_REFUSAL % "filtering")
+        return self.batcher.submit((prompt, flt))
 
     # ------------------------------------------------------------------ generation
     def _next_seed(self):
@@ -363,10 +385,10 @@ class RagService:
             ids = ids[len(ids) - limit:]  # keep the question and "Chatbot:" suffix
         return ids
 
-    def generate(self, user_prompt, params=None, debug=False):
-        """Synchronous /generate (thread-safe)."""
+    def generate(self, user_prompt, params=None, debug=False, filenames=None):
+        """Synchronous /generate (thread-safe). filenames: only these documents supply the context."""
         tr = Trace("generate")
-        results, rspans = self.retrieve(user_prompt)
+        results, rspans = self.retrieve(user_prompt, filenames)
         for k, v in rspans.items():
             tr.spans[k] = v
         log.debug("User query: %s", user_prompt)
@@ -404,8 +426,9 @@ class RagService:
             out["generated_tokens"] = len(s.out)
         return out
 
-    def generate_batch(self, prompts, params=None, seeds=None):
+    def generate_batch(self, prompts, params=None, seeds=None, filters=None):
         """Many queries at once (benchmark / offline): one embed + one search + one engine run.
+        filters: per prompt None or the filenames its context must come from.
         Must not be mixed with the background loop (call with start_threads=False).
 
         Tensor parallel (every TP rank calls this with the same arguments): the TP leader embeds,
@@ -424,7 +447,10 @@ class RagService:
         ctxs, fulls = [None] * n, [None] * n
         if lead:
             q = self.embedder.embed(list(prompts))
-            res = self.store.search(q, self.cfg.retrieve_k)
+            if filters is not None and any(f for f in filters):
+                res = self.store.search(q, self.cfg.retrieve_k, filters=[self._filter(f) for f in filters])
+            else:
+                res = self.store.search(q, self.cfg.retrieve_k)
             for i, (p, r) in enumerate(zip(prompts, res)):
                 if r:
                     ctxs[i] = build_context(r, self.cfg.context_k)
@@ -506,12 +532,18 @@ class RagService:
         return outs
 
     # ------------------------------------------------------------------ ingest
-    def ingest_pdf_bytes(self, filename, data, persist=True):
-        """Reference upload_pdf/process_pdf: extract -> chunk -> embed -> update_index."""
+    def ingest_pdf_bytes(self, filename, data, persist=True, replace=False):
+        """Reference upload_pdf/process_pdf: extract -> chunk -> embed -> update_index.
+        replace: the document's old chunks are deleted and the new ones added under one store lock (without
+        it a re-upload only adds chunks whose ids are new)."""
+        if replace and getattr(self.store, "sharded", False):
+            raise ValueError(self.store.SHARDED_REFUSAL % "replace")
         text = pdfmod.extract_text(data)
         chunks = split_text(text, self.cfg.chunk_words, self.cfg.chunk_overlap)
+        if replace and not chunks:  # a revision without text: the old chunks still go
+            self.delete_document(filename)
         if chunks:
-            args = (filename, chunks, not self.cfg.reingest_append, persist)
+            args = (filename, chunks, not self.cfg.reingest_append, persist) + ((True,) if replace else ())
             if self.collective:  # tensor-parallel server: every rank embeds a share (data-parallel ingest)
                 self.loop.run_job("ingest", args, timeout=self.cfg.request_timeout_s)
             else:
@@ -544,6 +576,17 @@ class RagService:
     def index_info(self):
         self.store.maybe_reload()
         return self.store.info()
+
+    def documents(self):
+        self.store.maybe_reload()
+        return self.store.documents()
+
+    def delete_document(self, filename):
+        """Remove a document's chunks (gone for the next search; compacted away by the next snapshot).
+        Replicated tensor-parallel serving keeps the store on rank 0 only, so this is no collective job."""
+        n = self.store.delete(filename)
+        metrics.set_gauge("index", self.store.index.ntotal)
+        return n
 
     def health(self):
         comm = getattr(self.engine, "comm", None)

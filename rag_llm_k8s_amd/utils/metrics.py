@@ -40,6 +40,12 @@ def registry():
         _M["batch"] = prom.Gauge("rag_decode_batch", "running sequences after the last engine step", registry=_REG)
         _M["kv_free"] = prom.Gauge("rag_kv_free_blocks", "free KV-cache blocks", registry=_REG)
         _M["index"] = prom.Gauge("rag_index_vectors", "vectors in the index", registry=_REG)
+        _M["index_chunks_deleted"] = prom.Counter("rag_index_chunks_deleted_total", "chunks removed by document "
+                                                  "delete / replace", registry=_REG)
+        _M["index_compactions"] = prom.Counter("rag_index_compactions_total", "index compactions (tombstoned "
+                                               "chunks dropped before a snapshot)", registry=_REG)
+        _M["index_tombstones"] = prom.Gauge("rag_index_tombstoned_chunks", "deleted chunks still resident "
+                                            "(masked out of every search until the next compaction)", registry=_REG)
         _M["hbm"] = prom.Gauge("rag_hbm_bytes_allocated", "HBM allocated by torch", registry=_REG)
     return _REG
 

@@ -155,6 +155,12 @@ def main():
         t = timeit(lambda: N.l2_search(xt, n, n, qv, 4), iters=5, warmup=1)
         rows.append(dict(kind="l2_search", N=n, d=d, nq=32, ours_us=t * 1e6, TBps=n * d * 4 / t / 1e12))
         print(rows[-1], flush=True)
+        # the filtered search beside it: one all-ones bitmap row (tools/bench_filtered_search.py has the A/B)
+        ones = torch.full((1, (n + 31) // 32), -1, dtype=torch.int32, device=dev)
+        qm = torch.zeros(32, dtype=torch.int32, device=dev)
+        t = timeit(lambda: N.l2_search(xt, n, n, qv, 4, masks=ones, qmask=qm), iters=5, warmup=1)
+        rows.append(dict(kind="l2_search_masked", N=n, d=d, nq=32, ours_us=t * 1e6, TBps=n * d * 4 / t / 1e12))
+        print(rows[-1], flush=True)
 
     os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
     with open(args.out, "w") as f:
