@@ -72,6 +72,12 @@ class RagConfig:
     index_recovery: str = "rebuild"  # rebuild (quarantine unreadable index, re-ingest PDF_DIR) | fail
     ignore_eos: bool = False  # benchmarks only: every request generates exactly max_new_tokens
     index_sharded: bool = False  # TP server: each rank keeps a row shard of the index, search is collective
+    # second-stage retrieval (opt-in): a cross-encoder directory (BERT / XLM-R *ForSequenceClassification with
+    # one label); the search returns rerank_candidates chunks and the best retrieve_k by its score are kept
+    rerank_model: str = ""  # empty = off
+    rerank_candidates: int = 32  # retrieve_k <= N <= 64 (the width of the search kernels' top lists)
+    rerank_max_len: int = 512  # tokens per (query, chunk) pair; capped by the model's positions
+    rerank_batch_tokens: int = 65536
     extra: dict = field(default_factory=dict)
 
     @classmethod
@@ -94,6 +100,8 @@ class RagConfig:
             "STEP_TIMEOUT_S": ("step_timeout_s", float), "WATCHDOG_EXIT": ("watchdog_exit", bool),
             "INDEX_RECOVERY": ("index_recovery", str), "IGNORE_EOS": ("ignore_eos", bool),
             "INDEX_SHARDED": ("index_sharded", bool), "KV_CACHE_DTYPE": ("kv_cache_dtype", str),
+            "RERANK_MODEL": ("rerank_model", str), "RERANK_CANDIDATES": ("rerank_candidates", int),
+            "RERANK_MAX_LEN": ("rerank_max_len", int), "RERANK_BATCH_TOKENS": ("rerank_batch_tokens", int),
         }
         for env, (attr, cast) in m.items():
             setattr(c, attr, _env(env, getattr(c, attr), cast))
@@ -107,7 +115,20 @@ class RagConfig:
         c.kv_cache_dtype = str(c.kv_cache_dtype).strip().lower()
         if c.kv_cache_dtype not in ("bf16", "fp8"):
             raise ValueError("KV_CACHE_DTYPE must be bf16 or fp8, got %r" % c.kv_cache_dtype)
+        c.validate_rerank()
         return c
+
+    RERANK_MAX_CANDIDATES = 64
+
+    def validate_rerank(self):
+        """With a reranker configured, the candidate count must cover retrieve_k and fit the kernels' lists."""
+        if not self.rerank_model:
+            return
+        if not self.retrieve_k <= self.rerank_candidates <= self.RERANK_MAX_CANDIDATES:
+            raise ValueError("RERANK_CANDIDATES must be in RETRIEVE_K..%d (retrieve_k = %d), got %d"
+                             % (self.RERANK_MAX_CANDIDATES, self.retrieve_k, self.rerank_candidates))
+        if self.rerank_max_len < 8 or self.rerank_batch_tokens < self.rerank_max_len:
+            raise ValueError("RERANK_MAX_LEN must be >= 8 and RERANK_BATCH_TOKENS >= RERANK_MAX_LEN")
 
     def resolved_device(self) -> str:
         if self.device != "auto":

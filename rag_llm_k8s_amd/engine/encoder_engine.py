@@ -18,6 +18,21 @@ import torch
 PIPELINE_GROUP = 2048  # texts per tokenise/encode pipeline stage
 
 
+def pack_batches(lens, max_batch_tokens):
+    """Greedy varlen packing shared by the embedding and reranking engines: sequences in descending
+    length order (stable), as many per batch as fit in max_batch_tokens (at least one). Yields
+    (rows, row_lens): the original indices of a batch's sequences and their lengths, in packed order."""
+    n = len(lens)
+    order = np.argsort(-np.asarray(lens).astype(np.int64), kind="stable")
+    slens = np.asarray(lens)[order].astype(np.int64)
+    i = 0
+    while i < n:
+        csum = np.cumsum(slens[i:])
+        j = i + max(1, int(np.searchsorted(csum, max_batch_tokens, side="right")))
+        yield order[i:j], slens[i:j]
+        i = j
+
+
 class EmbeddingEngine:
     def __init__(self, model, tokenizer, max_batch_tokens: int = 65536):
         self.model = model
@@ -59,19 +74,11 @@ class EmbeddingEngine:
             return out
         starts = np.zeros(n + 1, dtype=np.int64)
         np.cumsum(lens, out=starts[1:])
-        order = np.argsort(-lens.astype(np.int64), kind="stable")
-        slens = lens[order].astype(np.int64)
-        i = 0
-        while i < n:
-            # greedy packing in descending length order: as many sequences as fit in max_batch_tokens
-            csum = np.cumsum(slens[i:])
-            j = i + max(1, int(np.searchsorted(csum, self.max_batch_tokens, side="right")))
-            rows = order[i:j]
+        for rows, row_lens in pack_batches(lens, self.max_batch_tokens):
             flat = np.concatenate([ids[starts[r]:starts[r + 1]] for r in rows])
             t = torch.from_numpy(flat).to(self.device)  # pageable source: a synchronous copy, safe to reuse
-            emb = self.model.forward_packed(t, [int(x) for x in slens[i:j]])
+            emb = self.model.forward_packed(t, [int(x) for x in row_lens])
             out[torch.from_numpy(rows + row0).to(self.device)] = emb
-            i = j
         return out
 
     def embed(self, texts):

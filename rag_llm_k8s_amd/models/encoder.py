@@ -113,8 +113,10 @@ class EncoderWeights:
 
         w.word = g("embeddings.word_embeddings.weight")
         w.pos = g("embeddings.position_embeddings.weight")
-        w.type_row = g("embeddings.token_type_embeddings.weight")[0].contiguous()
+        w.type_table = g("embeddings.token_type_embeddings.weight")
+        w.type_row = w.type_table[0].contiguous()
         w.ln_g, w.ln_b = g("embeddings.LayerNorm.weight"), g("embeddings.LayerNorm.bias")
+        w.head = cls._head_from_hf(cfg, get, has, prefix, device, dtype)
         w.layers = []
         for i in range(cfg.num_hidden_layers):
             p = "encoder.layer.%d." % i
@@ -128,6 +130,47 @@ class EncoderWeights:
                 wo2=g(p + "output.dense.weight"), bo2=g(p + "output.dense.bias"),
                 ln2_g=g(p + "output.LayerNorm.weight"), ln2_b=g(p + "output.LayerNorm.bias")))
         return w
+
+    @staticmethod
+    def _head_from_hf(cfg, get, has, prefix, device, dtype):
+        """The one-label sequence-classification head, as (W1, b1, w2, b2), or None for a bare encoder.
+        XLMRobertaForSequenceClassification: classifier.dense -> tanh -> classifier.out_proj.
+        BertForSequenceClassification: bert.pooler.dense -> tanh -> classifier."""
+        if has("classifier.dense.weight"):
+            names = ("classifier.dense", "classifier.out_proj")
+        elif has("classifier.weight"):
+            names = (prefix + "pooler.dense", "classifier")
+            if not has(names[0] + ".weight"):
+                raise ValueError("checkpoint has a classifier but no %s.weight" % names[0])
+        else:
+            return None
+        out_w = get(names[1] + ".weight")
+        if out_w.dim() != 2 or out_w.shape[0] != 1:
+            raise ValueError("reranker checkpoint must have num_labels == 1 (a single relevance score), got "
+                             "a head with %d labels" % (out_w.shape[0] if out_w.dim() == 2 else -1))
+
+        def h(n):
+            return get(n).to(device=device, dtype=dtype).contiguous()
+
+        w2 = h(names[1] + ".weight").reshape(-1).contiguous()
+        b2 = float(get(names[1] + ".bias").to(dtype).float().reshape(-1)[0])
+        return dict(w1=h(names[0] + ".weight"), b1=h(names[0] + ".bias"), w2=w2, b2=b2)
+
+    def to(self, device):
+        """A copy of these weights on another device."""
+        def mv(v):
+            if torch.is_tensor(v):
+                return v.to(device)
+            if isinstance(v, dict):
+                return {k: mv(x) for k, x in v.items()}
+            if isinstance(v, list):
+                return [mv(x) for x in v]
+            return v
+
+        out = type(self)()
+        for k, v in vars(self).items():
+            setattr(out, k, mv(v))
+        return out
 
     @classmethod
     def from_dir(cls, cfg, path, device):
@@ -144,11 +187,13 @@ class EncoderWeights:
         return cls.from_hf(cfg, lambda n: sd[n], lambda n: n in sd, device)
 
     @classmethod
-    def random(cls, cfg: EncoderConfig, device, seed=0, dtype=torch.bfloat16):
+    def random(cls, cfg: EncoderConfig, device, seed=0, dtype=torch.bfloat16, head=False, head_scale=1.0, std=0.02):
+        """head: also a one-label classification head, its matrices of std head_scale / sqrt(H) (a 0.02-std
+        head gives nearly constant scores); std: spread of every other matrix."""
         gen = torch.Generator(device=device).manual_seed(seed)
         H, I = cfg.hidden_size, cfg.intermediate_size
 
-        def r(*s, std=0.02):
+        def r(*s, std=std):
             return (torch.randn(*s, device=device, generator=gen) * std).to(dtype)
 
         def one(n):
@@ -160,6 +205,13 @@ class EncoderWeights:
         w.layers = [dict(wqkv=r(3 * H, H), bqkv=r(3 * H), wo=r(H, H), bo=r(H), ln1_g=one(H), ln1_b=r(H),
                          wi=r(I, H), bi=r(I), wo2=r(H, I), bo2=r(H), ln2_g=one(H), ln2_b=r(H))
                     for _ in range(cfg.num_hidden_layers)]
+        # drawn after everything above, so the embedder weights of a seed are what they always were
+        rows = [w.type_row.reshape(1, H)] + [r(1, H) for _ in range(max(1, cfg.type_vocab_size) - 1)]
+        w.type_table = torch.cat(rows, 0).contiguous()
+        w.head = None
+        if head:
+            w.head = dict(w1=r(H, H, std=head_scale / H ** 0.5), b1=r(H), w2=r(H, std=head_scale / H ** 0.5),
+                          b2=float(r(1)[0]))
         return w
 
 
@@ -176,6 +228,21 @@ class EncoderModel:
     def forward_packed(self, ids: torch.Tensor, lens):
         """ids: int32 [T] packed token ids (on device), lens: python list of sequence lengths.
         Returns fp32 [B, H] pooled (+ normalised) sentence embeddings."""
+        h, cu = self.hidden_packed(ids, lens)
+        return self.be.pool_l2norm(h, cu, mode=self.cfg.pooling, normalize=self.cfg.normalize)
+
+    def score_packed(self, ids: torch.Tensor, lens, type_ids=None):
+        """Cross-encoder relevance scores, fp32 [B]: the encoder, then the classification head on each
+        sequence's first token."""
+        hd = getattr(self.w, "head", None)
+        if hd is None:
+            raise ValueError("this encoder checkpoint has no sequence-classification head")
+        h, cu = self.hidden_packed(ids, lens, type_ids)
+        return self.be.cls_head(h, cu, hd["w1"], hd["b1"], hd["w2"], hd["b2"])
+
+    def hidden_packed(self, ids: torch.Tensor, lens, type_ids=None):
+        """Last-layer hidden states bf16 [T, H] of the packed sequences and cu int32 [B + 1] (on device).
+        type_ids: int32 [T] token-type ids (BERT sentence pairs); None adds type row 0 to every token."""
         from ..ops.native import build_prefill_tiles
 
         be, w, c = self.be, self.w, self.cfg
@@ -187,7 +254,10 @@ class EncoderModel:
         cu = torch.tensor(cu_host, dtype=torch.int32).to(dev)
         pos = self.position_ids(lens).to(dev)
         tiles = build_prefill_tiles(lens, nh, nh).to(dev) if dev.type == "cuda" else None
-        h = be.embed_ln(ids, pos, w.word, w.pos, w.type_row, w.ln_g, w.ln_b, c.layer_norm_eps)
+        if type_ids is None:
+            h = be.embed_ln(ids, pos, w.word, w.pos, w.type_row, w.ln_g, w.ln_b, c.layer_norm_eps)
+        else:
+            h = be.embed_ln_tt(ids, pos, type_ids, w.word, w.pos, w.type_table, w.ln_g, w.ln_b, c.layer_norm_eps)
         T = h.shape[0]
         attn = torch.empty((T, H), dtype=h.dtype, device=dev)
         for L in w.layers:
@@ -198,4 +268,4 @@ class EncoderModel:
             f = be.gemm(h, L["wi"], bias=L["bi"], epi="bias_gelu")
             a = be.gemm(f, L["wo2"], bias=L["bo2"], resid=h, epi="bias_resid")
             h = be.layernorm(a, L["ln2_g"], L["ln2_b"], c.layer_norm_eps)
-        return be.pool_l2norm(h, cu, mode=c.pooling, normalize=c.normalize)
+        return h, cu

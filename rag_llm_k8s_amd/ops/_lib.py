@@ -64,6 +64,10 @@ _SIGS = {
     "ragk_embed": [P, P, P, I, I, I, S],
     "ragk_embed_carry": [P, P, P, P, P, I, I, I, S],
     "ragk_embed_ln": [P, P, P, P, P, P, P, P, I, I, F, I, S],
+    # csrc/kernels/rerank.hip (cross-encoder reranking)
+    "ragk_embed_ln_tt": [P, P, P, P, P, P, I, P, P, P, I, I, F, S],
+    "ragk_cls_head": [P, I, I, P, P, P, P, F, P, I, I, S],
+    "ragk_rerank_select": [P, P, P, P, P, P, P, I, I, I, S],
     "ragk_rope_kv": [P, I, P, P, P, P, P, P, I, I, I, I, I, I, S],
     "ragk_pool_l2norm": [P, I, P, P, I, I, I, I, S],
     "ragk_silu_mul": [P, I, P, I, I, I, S],

@@ -227,6 +227,18 @@ class TorchBackend:
     def pool_l2norm(self, hidden, cu, mode="cls", normalize=True):
         return R.pool_l2norm(hidden, cu.cpu(), mode=mode, normalize=normalize)
 
+    # cross-encoder reranking ---------------------------------------------------
+    def embed_ln_tt(self, ids, pos_ids, type_ids, word, pos, type_table, g, b, eps):
+        return R.embed_ln_tt(ids, pos_ids, type_ids, word, pos, type_table, g, b, eps)
+
+    def cls_head(self, h, cu, w1, b1, w2, b2):
+        return R.cls_head(h, cu, w1, b1, w2, b2)
+
+    def rerank_select(self, scores, cand_ids, cand_dist, n_valid, k):
+        if not 1 <= scores.shape[1] <= R.SELECT_MAX_N or not 1 <= k <= scores.shape[1]:
+            raise ValueError("rerank_select: need 1 <= k <= N <= %d" % R.SELECT_MAX_N)
+        return R.rerank_select(scores, cand_ids, cand_dist, n_valid, k)
+
     # sampling -----------------------------------------------------------------
     def topk_candidates(self, logits, K, vocab_offset=0, max_cand=512, chunks=None):
         k = min(K, logits.shape[1])
@@ -376,6 +388,15 @@ class NativeBackend(TorchBackend):
 
     def pool_l2norm(self, hidden, cu, mode="cls", normalize=True):
         return self.n.pool_l2norm(hidden, cu, mode=mode, normalize=normalize)
+
+    def embed_ln_tt(self, ids, pos_ids, type_ids, word, pos, type_table, g, b, eps):
+        return self.n.embed_ln_tt(ids, pos_ids, type_ids, word, pos, type_table, g, b, eps)
+
+    def cls_head(self, h, cu, w1, b1, w2, b2):
+        return self.n.cls_head(h, cu, w1, b1, w2, b2)
+
+    def rerank_select(self, scores, cand_ids, cand_dist, n_valid, k):
+        return self.n.rerank_select(scores, cand_ids, cand_dist, n_valid, k)
 
     def topk_candidates(self, logits, K, vocab_offset=0, max_cand=512, chunks=None):
         return self.n.topk_candidates(logits, K, vocab_offset=vocab_offset, max_cand=max_cand, chunks=chunks)

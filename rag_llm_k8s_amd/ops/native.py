@@ -924,6 +924,82 @@ def embed_ln(ids, pos_ids, word, pos, type_row, g, b, eps, do_ln=True, out=None)
     return out
 
 
+def embed_ln_tt(ids, pos_ids, type_ids, word, pos, type_table, g, b, eps, out=None):
+    """LN(word[id] + pos[pos_id] + type_table[type_id]): embed_ln with per-token type ids (cross-encoders)."""
+    T = int(ids.numel())
+    for t, name in ((ids, "ids"), (pos_ids, "pos_ids"), (type_ids, "type_ids")):
+        _req(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and int(t.numel()) == T, "%s: int32 [T]" % name)
+    _bf16_2d(word, "word")
+    _bf16_2d(pos, "pos")
+    _bf16_2d(type_table, "type_table")
+    H = word.shape[1]
+    _req(H % 8 == 0 and H <= 8192, "H must be a multiple of 8, at most 8192")
+    _req(pos.shape[1] == H and type_table.shape[1] == H and type_table.shape[0] >= 1, "table widths")
+    _req(word.is_contiguous() and pos.is_contiguous() and type_table.is_contiguous(), "contiguous tables")
+    _req(g.dtype == torch.bfloat16 and b.dtype == torch.bfloat16 and g.numel() == H and b.numel() == H, "LN weights")
+    out = torch.empty((T, H), dtype=word.dtype, device=word.device) if out is None else out
+    _req(out.shape == (T, H) and out.is_contiguous(), "out")
+    for t, name in ((word, "word"), (pos, "pos"), (type_table, "type_table"), (g, "g"), (b, "b"), (out, "out")):
+        _al16(t, name)
+    check(_lib.lib().ragk_embed_ln_tt(ids.data_ptr(), pos_ids.data_ptr(), type_ids.data_ptr(), word.data_ptr(),
+                                      pos.data_ptr(), type_table.data_ptr(), type_table.shape[0], g.data_ptr(),
+                                      b.data_ptr(), out.data_ptr(), T, H, float(eps), stream_ptr()), "ragk_embed_ln_tt")
+    return out
+
+
+CLS_HEAD_MAX_H = 1024  # the 16 gathered CLS rows live in LDS
+
+
+def cls_head(h, cu, w1, b1, w2, b2, out=None):
+    """fp32 [B] scores: w2 . tanh(W1 . h[cu[b]] + b1) + b2, one launch (16 sequences per workgroup).
+    H: a multiple of 64 up to 1024 (384, 768 and 1024 are the cross-encoders in use; 128 the test models)."""
+    _bf16_2d(h, "h")
+    T, H = h.shape
+    _req(H % 64 == 0 and 64 <= H <= CLS_HEAD_MAX_H,
+         "cls_head: H must be a multiple of 64 in 64..%d (got %d)" % (CLS_HEAD_MAX_H, H))
+    _req(T >= 1, "cls_head: empty hidden states")
+    _req(cu.is_cuda and cu.dtype == torch.int32 and cu.is_contiguous() and cu.numel() >= 1, "cu: int32 [B + 1]")
+    B = cu.numel() - 1
+    _bf16_2d(w1, "w1")
+    _req(tuple(w1.shape) == (H, H) and w1.is_contiguous(), "w1: [H, H]")
+    for t, name in ((b1, "b1"), (w2, "w2")):
+        _req(t.is_cuda and t.dtype == torch.bfloat16 and t.numel() == H and t.is_contiguous(), "%s: bf16 [H]" % name)
+    _al16(h, "h")
+    _al16(w1, "w1")
+    out = torch.empty((B,), dtype=torch.float32, device=h.device) if out is None else out
+    _req(out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= B, "out: fp32 [B]")
+    check(_lib.lib().ragk_cls_head(h.data_ptr(), h.stride(0), T, cu.data_ptr(), w1.data_ptr(), b1.data_ptr(),
+                                   w2.data_ptr(), float(b2), out.data_ptr(), B, H, stream_ptr()), "ragk_cls_head")
+    return out
+
+
+def rerank_select(scores, cand_ids, cand_dist, n_valid, k, out=None):
+    """Segmented stable top-k by score (descending, ties in candidate order, NaN last). Returns
+    (ids int64 [Q, k], dist fp32 [Q, k], score fp32 [Q, k]); slots past n_valid are (-1, FLT_MAX, -FLT_MAX)."""
+    _req(scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2 and scores.is_contiguous(), "scores")
+    Q, N = scores.shape
+    _req(1 <= N <= 64, "rerank_select: N must be in 1..64 (got %d)" % N)
+    _req(1 <= k <= N, "rerank_select: k must be in 1..N (got %d)" % k)
+    _req(cand_ids.is_cuda and cand_ids.dtype == torch.int64 and tuple(cand_ids.shape) == (Q, N)
+         and cand_ids.is_contiguous(), "cand_ids: int64 [Q, N]")
+    _req(cand_dist.is_cuda and cand_dist.dtype == torch.float32 and tuple(cand_dist.shape) == (Q, N)
+         and cand_dist.is_contiguous(), "cand_dist: fp32 [Q, N]")
+    _req(n_valid.is_cuda and n_valid.dtype == torch.int32 and n_valid.numel() == Q and n_valid.is_contiguous(),
+         "n_valid: int32 [Q]")
+    if out is None:
+        out = (torch.empty((Q, k), dtype=torch.int64, device=scores.device),
+               torch.empty((Q, k), dtype=torch.float32, device=scores.device),
+               torch.empty((Q, k), dtype=torch.float32, device=scores.device))
+    oi, od, os_ = out
+    _req(oi.dtype == torch.int64 and od.dtype == torch.float32 and os_.dtype == torch.float32, "out dtypes")
+    for t in out:
+        _req(t.is_contiguous() and t.numel() >= Q * k, "out: [Q, k]")
+    check(_lib.lib().ragk_rerank_select(scores.data_ptr(), cand_ids.data_ptr(), cand_dist.data_ptr(),
+                                        n_valid.data_ptr(), oi.data_ptr(), od.data_ptr(), os_.data_ptr(), Q, N, k,
+                                        stream_ptr()), "ragk_rerank_select")
+    return out
+
+
 def rope_kv(qkv, positions, cos_t, sin_t, slots, k_cache, v_cache, Hq, Hkv, D, apply_rope=True):
     """In-place RoPE on q and k (inside qkv [T, (Hq+2Hkv)*D]) + paged cache write."""
     _bf16_2d(qkv, "qkv")

@@ -158,6 +158,54 @@ def pool_l2norm(hidden, cu, mode="cls", normalize=True):
     return F.normalize(o, p=2, dim=-1) if normalize else o
 
 
+# ---- cross-encoder reranking (csrc/kernels/rerank.hip) ------------------------------------------------
+SELECT_MAX_N = 64  # one wave lane per candidate; also the width of the search kernels' top lists
+
+
+def embed_ln_tt(ids, pos_ids, type_ids, word, pos, type_table, g, b, eps):
+    """LN(word[id] + pos[pos_id] + type_table[type_id]) in fp32, cast to the table dtype."""
+    h = word[ids.long()].float() + pos[pos_ids.long()].float()
+    h = h + type_table[type_ids.long()].float()
+    return F.layer_norm(h, (h.shape[-1],), g.float(), b.float(), eps).to(word.dtype)
+
+
+def cls_head(h, cu, w1, b1, w2, b2, dtype=torch.float32):
+    """score[b] = w2 . tanh(W1 . h[cu[b]] + b1) + b2 (HF sequence-classification heads with one label)."""
+    x = h[cu[:-1].long()].to(dtype)
+    y = torch.tanh(x @ w1.to(dtype).t() + b1.to(dtype))
+    return y @ w2.to(dtype).reshape(-1) + float(b2)
+
+
+def _select_beats(sj, j, si, i):
+    nj, ni = sj != sj, si != si
+    if nj:
+        return ni and j < i
+    if ni:
+        return True
+    return sj > si or (sj == si and j < i)
+
+
+def rerank_select(scores, cand_ids, cand_dist, n_valid, k):
+    """Per query: the k best of the first n_valid candidates by score descending; ties keep the candidate
+    order, NaN ranks last; slots past n_valid are (-1, FLT_MAX, -FLT_MAX). Bits of the inputs are copied."""
+    import functools
+
+    Q, N = scores.shape
+    fmax = torch.finfo(torch.float32).max
+    oi = torch.full((Q, k), -1, dtype=torch.int64)
+    od = torch.full((Q, k), fmax, dtype=torch.float32)
+    os_ = torch.full((Q, k), -fmax, dtype=torch.float32)
+    sc = scores.float().cpu()
+    for q in range(Q):
+        nv = max(0, min(int(n_valid[q]), N))
+        s = [float(x) for x in sc[q, :nv]]
+        order = sorted(range(nv), key=functools.cmp_to_key(
+            lambda a, b: -1 if _select_beats(s[a], a, s[b], b) else 1))
+        for r, c in enumerate(order[:k]):
+            oi[q, r], od[q, r], os_[q, r] = cand_ids[q, c], cand_dist[q, c], sc[q, c]
+    return oi, od, os_
+
+
 def sample_from_logits(logits, temperature, top_k, top_p, u=None):
     """Single-row HF-order sampler (temperature -> top-k -> top-p). Returns (kept token
     ids in descending-prob order, probabilities, pick). `u` in [0,1) draws the token."""

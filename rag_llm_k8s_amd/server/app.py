@@ -11,6 +11,8 @@ Routes (exact request/response/error contract):
 New: GET /healthz (liveness), GET /readyz (weights + index loaded), GET /metrics (Prometheus).
 New (documents can be listed, removed, replaced and filtered on; the reference can only add):
   POST /generate     optional "filenames": [str, ...] -> the context comes from these documents only
+  POST /generate     optional "rerank": false -> skip the cross-encoder stage for this query (RERANK_MODEL set);
+                     "rerank": true without RERANK_MODEL -> 500 {"error"} naming it
   POST /upload_pdf?replace=1 (or form field replace=1) -> the document's old chunks are replaced
   GET  /documents    -> {"documents": [{"filename", "chunks"}]}
   DELETE /documents/<filename> -> 200 {"message", "chunks_removed"} | 404 {"error"}
@@ -36,10 +38,10 @@ def create_app(service) -> Flask:
             user_prompt = data.get("prompt", "")
             debug = bool(data.get("debug", False))
             filenames = data.get("filenames")
-            if filenames:
-                out = service.generate(user_prompt, debug=debug, filenames=filenames)
-            else:
-                out = service.generate(user_prompt, debug=debug)
+            kw = {"filenames": filenames} if filenames else {}
+            if data.get("rerank") is not None:  # per-request switch of the cross-encoder stage
+                kw["rerank"] = bool(data["rerank"])
+            out = service.generate(user_prompt, debug=debug, **kw)
             metrics.inc("requests", route="generate", status="200")
             return jsonify(out)
         except Exception as e:

@@ -100,6 +100,37 @@ def build_embedder(cfg, device):
     return EmbeddingEngine(EncoderModel(ec, w, device), Tokenizer(path), max_batch_tokens=cfg.embed_batch_tokens)
 
 
+def build_reranker(cfg, device):
+    """RERANK_MODEL: a local cross-encoder directory (config.json, model.safetensors, tokenizer.json of a BERT /
+    XLM-R *ForSequenceClassification checkpoint with one label). Empty = no second stage."""
+    if not cfg.rerank_model:
+        return None
+    from ..engine.rerank_engine import Reranker
+    from ..models.encoder import EncoderConfig, EncoderModel, EncoderWeights
+    from ..runtime.tokenizer import Tokenizer
+
+    cfg.validate_rerank()
+    path = cfg.rerank_model
+    if not os.path.isdir(path):
+        raise FileNotFoundError("RERANK_MODEL=%s is not a local model directory (the framework never downloads "
+                                "at startup)" % path)
+    mcfg = _load_json(os.path.join(path, "config.json"))
+    if mcfg is None:
+        raise FileNotFoundError("no config.json under RERANK_MODEL=%s" % path)
+    labels = mcfg.get("num_labels", len(mcfg["id2label"]) if mcfg.get("id2label") else 1)
+    if labels != 1:
+        raise ValueError("RERANK_MODEL=%s has num_labels=%d; a reranker gives one relevance score" % (path, labels))
+    ec = EncoderConfig.from_dict(mcfg, pooling="cls")
+    w = EncoderWeights.from_dir(ec, path, device)
+    if w.head is None:
+        raise ValueError("RERANK_MODEL=%s has no sequence-classification head (classifier.* tensors)" % path)
+    rr = Reranker(EncoderModel(ec, w, device), Tokenizer(path), max_len=cfg.rerank_max_len,
+                  max_batch_tokens=cfg.rerank_batch_tokens)
+    log.info("Reranker loaded from %s: %d candidates -> %d, pairs of up to %d tokens", path, cfg.rerank_candidates,
+             cfg.retrieve_k, rr.max_len)
+    return rr
+
+
 def build_service(cfg, start_threads=True, tp_rank=0, tp_size=1, comm=None, tp_group=None, control=None):
     from ..index.store import DocumentStore
     from .rag_service import RagService
@@ -117,6 +148,7 @@ def build_service(cfg, start_threads=True, tp_rank=0, tp_size=1, comm=None, tp_g
     store = DocumentStore(cfg.index_path, embedder.dim, device=device, index_type=cfg.index_type,
                           ivf_nlist=cfg.ivf_nlist, ivf_nprobe=cfg.ivf_nprobe, recovery=cfg.index_recovery,
                           shard=shard)
+    reranker = build_reranker(cfg, device) if tp_rank == 0 else None  # like the query embedder: rank 0 retrieves
     svc = RagService(cfg, engine, tok, embedder, store, gen_config=gen, start_threads=start_threads, control=control,
-                     tp_group=tp_group if tp_size > 1 else None)
+                     tp_group=tp_group if tp_size > 1 else None, reranker=reranker)
     return svc

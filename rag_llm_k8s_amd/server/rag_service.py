@@ -261,12 +261,18 @@ class MicroBatcher(threading.Thread):
 
 class RagService:
     def __init__(self, cfg, llm_engine, llm_tokenizer, embedder, store, gen_config=None, start_threads=True,
-                 control=None, tp_group=None):
+                 control=None, tp_group=None, reranker=None):
         self.cfg = cfg
         self.engine = llm_engine
         self.tok = llm_tokenizer
         self.embedder = embedder
         self.store = store
+        # optional second stage (engine/rerank_engine.Reranker): the search returns rerank_candidates chunks
+        # and the cross-encoder keeps the best retrieve_k; None = the bi-encoder order goes into the prompt
+        self.reranker = reranker
+        if reranker is not None and not cfg.retrieve_k <= cfg.rerank_candidates <= cfg.RERANK_MAX_CANDIDATES:
+            raise ValueError("RERANK_CANDIDATES must be in RETRIEVE_K..%d (retrieve_k = %d), got %d"
+                             % (cfg.RERANK_MAX_CANDIDATES, cfg.retrieve_k, cfg.rerank_candidates))
         gen = gen_config or {}
         do_sample = cfg.do_sample if cfg.do_sample is not None else bool(gen.get("do_sample", True))
         eos = gen.get("eos_token_id")
@@ -323,11 +329,29 @@ class RagService:
             q = torch.zeros((0, self.store.dim), dtype=torch.float32)
         return self.store.search(q, k)
 
+    def _search_k(self, want):
+        """Candidates per query: rerank_candidates when any query of the batch goes through the reranker."""
+        return self.cfg.rerank_candidates if self.reranker is not None and any(want) else self.cfg.retrieve_k
+
+    def _second_stage(self, prompts, res, want):
+        """Rerank the result lists of the queries that want it (one scoring pass for all of them) and cut
+        every list to retrieve_k. The L2 distances stay with their chunks: build_context prints them."""
+        k = self.cfg.retrieve_k
+        out = [r[:k] for r in res]
+        rows = [i for i, w in enumerate(want) if w and res[i]]
+        if self.reranker is not None and rows:
+            for i, r in zip(rows, self.reranker.rerank([prompts[i] for i in rows], [res[i] for i in rows], k)):
+                out[i] = r
+        return out
+
     def _retrieve_batch(self, items):
-        """items: (prompt, filter) pairs -- filter None, or the filenames the context must come from. The
-        micro-batcher mixes requests, so one search carries a filter per query (a masked search)."""
-        prompts = [p for p, _ in items]
-        filters = [f for _, f in items]
+        """items: (prompt, filter[, rerank]) tuples -- filter None, or the filenames the context must come
+        from; rerank False skips the second stage for that query. The micro-batcher mixes requests, so one
+        search carries a filter per query (a masked search) and one batch may hold both kinds of query."""
+        prompts = [it[0] for it in items]
+        filters = [it[1] for it in items]
+        want = [self.reranker is not None and (len(it) < 3 or it[2] is not False) for it in items]
+        k_search = self._search_k(want)
         tr = Trace("retrieve")
         with tr.span("embed"):
             faults.check("embed_error")
@@ -335,11 +359,14 @@ class RagService:
         with tr.span("search"):
             self.store.maybe_reload()
             if self.collective and getattr(self.store, "sharded", False):
-                res = self.loop.run_job("search", (q.cpu(), self.cfg.retrieve_k), timeout=self.cfg.request_timeout_s)
+                res = self.loop.run_job("search", (q.cpu(), k_search), timeout=self.cfg.request_timeout_s)
             elif any(f is not None for f in filters):
-                res = self.store.search(q, self.cfg.retrieve_k, filters=filters)
+                res = self.store.search(q, k_search, filters=filters)
             else:
-                res = self.store.search(q, self.cfg.retrieve_k)
+                res = self.store.search(q, k_search)
+        if any(want):
+            with tr.span("rerank"):
+                res = self._second_stage(prompts, res, want)
         return [(r, tr.spans) for r in res]
 
     @staticmethod
@@ -351,11 +378,19 @@ class RagService:
             return (filenames,)
         return tuple(str(f) for f in filenames)
 
-    def retrieve(self, prompt, filenames=None):
+    def _rerank_flag(self, rerank):
+        """Request "rerank": absent = the configured default; true needs a configured model."""
+        if rerank is None:
+            return None
+        if rerank and self.reranker is None:
+            raise ValueError('"rerank": true needs a reranker: set RERANK_MODEL to a cross-encoder directory')
+        return bool(rerank)
+
+    def retrieve(self, prompt, filenames=None, rerank=None):
         flt = self._filter(filenames)
         if flt is not None and getattr(self.store, "sharded", False):  # refused before it joins a batch
             raise ValueError(self.store.SHARDED_REFUSAL % "filtering")
-        return self.batcher.submit((prompt, flt))
+        return self.batcher.submit((prompt, flt, self._rerank_flag(rerank)))
 
     # ------------------------------------------------------------------ generation
     def _next_seed(self):
@@ -385,10 +420,11 @@ class RagService:
             ids = ids[len(ids) - limit:]  # keep the question and "Chatbot:" suffix
         return ids
 
-    def generate(self, user_prompt, params=None, debug=False, filenames=None):
-        """Synchronous /generate (thread-safe). filenames: only these documents supply the context."""
+    def generate(self, user_prompt, params=None, debug=False, filenames=None, rerank=None):
+        """Synchronous /generate (thread-safe). filenames: only these documents supply the context.
+        rerank: False skips the cross-encoder stage for this request (None = on when one is configured)."""
         tr = Trace("generate")
-        results, rspans = self.retrieve(user_prompt, filenames)
+        results, rspans = self.retrieve(user_prompt, filenames, rerank)
         for k, v in rspans.items():
             tr.spans[k] = v
         log.debug("User query: %s", user_prompt)
@@ -424,11 +460,17 @@ class RagService:
             out["timings_ms"] = tr.summary_ms()
             out["prompt_tokens"] = len(ids)
             out["generated_tokens"] = len(s.out)
+            if self.reranker is not None:
+                out["retrieved"] = [{"filename": m.get("filename"), "chunk_id": m.get("chunk_id"),
+                                     "distance": float(d), "rerank_score": m.get("rerank_score")}
+                                    for m, d in results]
         return out
 
-    def generate_batch(self, prompts, params=None, seeds=None, filters=None):
+    def generate_batch(self, prompts, params=None, seeds=None, filters=None, rerank=None):
         """Many queries at once (benchmark / offline): one embed + one search + one engine run.
         filters: per prompt None or the filenames its context must come from.
+        rerank: per prompt (or one value for all) False to skip the cross-encoder stage; None = on when a
+        reranker is configured. With a reranker the outputs also carry "_retrieved": [(filename, chunk_id)].
         Must not be mixed with the background loop (call with start_threads=False).
 
         Tensor parallel (every TP rank calls this with the same arguments): the TP leader embeds,
@@ -445,13 +487,21 @@ class RagService:
         lead = (not tp) or comm.rank == 0
         n = len(prompts)
         ctxs, fulls = [None] * n, [None] * n
+        got = [None] * n
         if lead:
+            flags = list(rerank) if isinstance(rerank, (list, tuple)) else [rerank] * n
+            want = [self.reranker is not None and self._rerank_flag(f) is not False for f in flags]
+            k_search = self._search_k(want)
             q = self.embedder.embed(list(prompts))
             if filters is not None and any(f for f in filters):
-                res = self.store.search(q, self.cfg.retrieve_k, filters=[self._filter(f) for f in filters])
+                res = self.store.search(q, k_search, filters=[self._filter(f) for f in filters])
             else:
-                res = self.store.search(q, self.cfg.retrieve_k)
+                res = self.store.search(q, k_search)
+            if any(want):
+                res = self._second_stage(list(prompts), res, want)
             for i, (p, r) in enumerate(zip(prompts, res)):
+                if self.reranker is not None:
+                    got[i] = [(m.get("filename"), m.get("chunk_id")) for m, _ in r]
                 if r:
                     ctxs[i] = build_context(r, self.cfg.context_k)
                     fulls[i] = build_prompt(ctxs[i], p)
@@ -521,7 +571,7 @@ class RagService:
         if t_rest:  # when the helper thread had queued the tail prompts (after the head's first step)
             st["tail_queued_s"] = st.get("tail_queued_s", 0.0) + (t_rest[0] - t_prep)
         outs = []
-        for s, ctx in zip(seqs, ctxs):
+        for s, ctx, ret in zip(seqs, ctxs, got):
             if s is None:
                 outs.append({"generated_text": NO_RESULTS})
                 continue
@@ -529,6 +579,8 @@ class RagService:
             outs.append({"generated_text": text, "context": ctx, "_latency_s": s.t_done - t0,
                          "_ttft_s": (s.t_first or s.t_done) - t0, "_prompt_tokens": len(s.prompt),
                          "_gen_tokens": len(s.out)})
+            if ret is not None:
+                outs[-1]["_retrieved"] = ret
         return outs
 
     # ------------------------------------------------------------------ ingest

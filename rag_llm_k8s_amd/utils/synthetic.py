@@ -322,6 +322,49 @@ def write_encoder_checkpoint(out_dir, cfg, seed=0, wm=None):
             train_wordpiece_tokenizer(out_dir, wm, vocab=cfg.vocab_size)
 
 
+def cross_encoder_state_dict(cfg, seed=0, head_scale=1.0, std=0.02):
+    """encoder_state_dict under the *ForSequenceClassification names, plus a one-label head.
+    head_scale: std of the head matrices in units of 1/sqrt(H) -- a 0.02-std head gives nearly constant
+    scores, which would make any ordering test vacuous."""
+    xlmr = cfg.model_type == "xlm-roberta"
+    prefix = "roberta." if xlmr else "bert."
+    sd = {prefix + k: v for k, v in encoder_state_dict(cfg, seed, std).items()}
+    g = torch.Generator().manual_seed(seed + 7919)
+    H = cfg.hidden_size
+    hs = head_scale / H ** 0.5
+
+    def r(*s, sd_=std):
+        return (torch.randn(*s, generator=g) * sd_).bfloat16()
+
+    dense, out = ("classifier.dense", "classifier.out_proj") if xlmr else (prefix + "pooler.dense", "classifier")
+    sd[dense + ".weight"], sd[dense + ".bias"] = r(H, H, sd_=hs), r(H)
+    sd[out + ".weight"], sd[out + ".bias"] = r(1, H, sd_=hs), r(1)
+    return sd
+
+
+def write_cross_encoder_checkpoint(out_dir, cfg, seed=0, head_scale=1.0, wm=None, std=0.02):
+    """A random-init reranker in the HF *ForSequenceClassification layout (config with `architectures` and
+    num_labels 1, head tensors, tokenizer) -- what RERANK_MODEL points at; transformers loads it as is.
+    std: spread of the encoder's own matrices (wider than 0.02 makes the layers do visible work)."""
+    from ..runtime.safetensors_io import save_file
+
+    os.makedirs(out_dir, exist_ok=True)
+    d = cfg.to_hf_dict()
+    xlmr = cfg.model_type == "xlm-roberta"
+    d["architectures"] = ["XLMRobertaForSequenceClassification" if xlmr else "BertForSequenceClassification"]
+    d.update(num_labels=1, id2label={"0": "LABEL_0"}, label2id={"LABEL_0": 0}, hidden_dropout_prob=0.0,
+             attention_probs_dropout_prob=0.0, classifier_dropout=0.0)
+    with open(os.path.join(out_dir, "config.json"), "w") as f:
+        json.dump(d, f, indent=2)
+    save_file(cross_encoder_state_dict(cfg, seed, head_scale, std), os.path.join(out_dir, "model.safetensors"),
+              metadata={"format": "pt"})
+    if not os.path.exists(os.path.join(out_dir, "tokenizer.json")):
+        if xlmr:
+            train_xlmr_unigram_tokenizer(out_dir, wm, vocab=min(16000, cfg.vocab_size))
+        else:
+            train_wordpiece_tokenizer(out_dir, wm, vocab=cfg.vocab_size)
+
+
 def write_pdf_corpus(out_dir, n_docs, pages=4, words_per_page=600, wm=None, seed=0):
     from ..ingest.pdf import write_pdf
 

@@ -143,8 +143,12 @@ def build_workload(model="8b", embedder="minilm", n_chunks=10000, chunk_words=10
                    max_new_tokens=150, max_batch=32, max_model_len=8192, max_prefill_tokens=32768, device="cuda",
                    ctx=None, tp_comm=None, seed=0, use_graphs=True, index_type="flat", kv_blocks=None,
                    word_vocab=400000, dtype="bf16", index_vectors=0, start_threads=False, ignore_eos=False,
-                   mixed_prefill_tokens=0, progress=None, kv_dtype=None):
-    """`progress(msg)`: called after each setup stage (bench.py prints it: a 70B / 1M-vector setup runs
+                   mixed_prefill_tokens=0, progress=None, kv_dtype=None, reranker=None, rerank_candidates=32,
+                   rerank_max_len=512):
+    """`reranker`: None (off) or an encoder shape name ("tiny", "minilm", "bge-large"): a random-init
+    cross-encoder of that shape is attached as the second retrieval stage (BERT shapes: it shares the
+    embedder's WordPiece tokenizer), searching `rerank_candidates` chunks per query.
+    `progress(msg)`: called after each setup stage (bench.py prints it: a 70B / 1M-vector setup runs
     for minutes). `kv_dtype`: "bf16" | "fp8" KV cache; None takes the KV_CACHE_DTYPE environment variable
     (default bf16), so bench.py and tools/bench_serve.py can be A/B-run unmodified."""
     import os
@@ -166,9 +170,10 @@ def build_workload(model="8b", embedder="minilm", n_chunks=10000, chunk_words=10
             "tiny": lambda: L.llama_tiny(vocab=1024, layers=2, hidden=512, heads=4, kv_heads=2, inter=512),
             # TP=4/8 layouts: 8 KV heads (1 per rank at TP=8, as Llama-3.1 8B/70B), vocab % 8 != 0
             "tiny8": lambda: L.llama_tiny(vocab=1001, layers=2, hidden=512, heads=16, kv_heads=8, inter=1024)}[model]()
-    ecfg = {"minilm": E.minilm_l6, "bge-large": E.bge_large_en, "bge-m3": E.bge_m3,
-            "tiny": lambda: E.EncoderConfig(vocab_size=2048, hidden_size=128, num_hidden_layers=2,
-                                            num_attention_heads=4, intermediate_size=256, max_seq_length=128)}[embedder]()
+    shapes = {"minilm": E.minilm_l6, "bge-large": E.bge_large_en, "bge-m3": E.bge_m3,
+              "tiny": lambda: E.EncoderConfig(vocab_size=2048, hidden_size=128, num_hidden_layers=2,
+                                              num_attention_heads=4, intermediate_size=256, max_seq_length=128)}
+    ecfg = shapes[embedder]()
     xlmr = ecfg.model_type == "xlm-roberta"  # bge-m3: XLM-R embeddings (position offset) + Unigram ids
     enc_vocab = min(16000, ecfg.vocab_size) if xlmr else ecfg.vocab_size
     llm_tok, enc_tok = make_tokenizers(wm, lcfg.vocab_size, enc_vocab, ctx, "unigram" if xlmr else "wordpiece")
@@ -196,6 +201,17 @@ def build_workload(model="8b", embedder="minilm", n_chunks=10000, chunk_words=10
                        mixed_prefill_tokens=mixed_prefill_tokens, kv_dtype=kv_dtype)
     ew = E.EncoderWeights.random(ecfg, device, seed=seed + 1)
     emb = EmbeddingEngine(E.EncoderModel(ecfg, ew, device), enc_tok)
+    rr = None
+    if reranker is not None:
+        from ..engine.rerank_engine import Reranker
+
+        rcfg = shapes[reranker]()
+        if (rcfg.model_type == "xlm-roberta") != xlmr or rcfg.vocab_size != ecfg.vocab_size:
+            raise ValueError("the synthetic reranker shares the embedder's tokenizer: pick shapes of one family")
+        # wide matrices and head: a 0.02-std cross-encoder scores every pair alike. Drawn on the host, so a CPU
+        # and a GPU workload of one seed hold the same reranker (the device generators differ)
+        rw = E.EncoderWeights.random(rcfg, "cpu", seed=seed + 2, head=True, head_scale=3.0, std=0.1).to(device)
+        rr = Reranker(E.EncoderModel(rcfg, rw, device), enc_tok, max_len=rerank_max_len)
     t["weights_s"] = time.time() - t0
     say("weights %.1f s" % t["weights_s"])
 
@@ -206,7 +222,8 @@ def build_workload(model="8b", embedder="minilm", n_chunks=10000, chunk_words=10
     cfg = RagConfig(device=device, retrieve_k=retrieve_k, context_k=context_k, max_new_tokens=max_new_tokens,
                     max_batch=max_batch, max_model_len=max_model_len, index_path="/tmp/ragk_bench_index",
                     index_type=index_type, seed=seed, max_prefill_tokens=max_prefill_tokens, ignore_eos=ignore_eos,
-                    mixed_prefill_tokens=mixed_prefill_tokens, kv_cache_dtype=kv_dtype)
+                    mixed_prefill_tokens=mixed_prefill_tokens, kv_cache_dtype=kv_dtype,
+                    rerank_candidates=max(retrieve_k, rerank_candidates), rerank_max_len=rerank_max_len)
     n_index = max(n_chunks, index_vectors)
     store = DocumentStore(cfg.index_path, emb.dim, device=device, index_type=index_type,
                           ivf_nlist=4096 if n_index >= 500_000 else 1024)
@@ -244,7 +261,7 @@ def build_workload(model="8b", embedder="minilm", n_chunks=10000, chunk_words=10
     say("ingest %.1f s" % t["ingest_s"])
     svc = RagService(cfg, engine, llm_tok, emb, store, gen_config={"do_sample": True,
                                                                    "eos_token_id": lcfg.eos_token_id},
-                     start_threads=start_threads)
+                     start_threads=start_threads, reranker=rr)
     svc.ready = True
     return Workload(svc, wm, llm_tok, t, n_chunks)
 
