@@ -535,14 +535,20 @@ __device__ __forceinline__ void w4_read_f0(int g, const unsigned (&rbA)[2], cons
 
 // Output tile `tile` (of nwg) -> origin. Tiles are numbered so that the 8 XCDs each own a contiguous
 // range (xcd_remap; a persistent block keeps its XCD since the grid is a multiple of 8), grouped
-// WGROUP_M M-tiles deep for L2 reuse of the weight tiles.
-__device__ __forceinline__ void w4_origin(int tile, int nwg, int tiles_m, int tiles_n, int& m0, int& n0) {
+// WGROUP_M M-tiles deep for L2 reuse of the weight tiles. MT: tiles_m counts the entries of the M-tile
+// list mt and the i-th M-tile of the numbering is the real 256-row tile mt[i] (clamped to the last real
+// tile, mt_max, so a bad list can repeat work but never leaves the operands).
+template <bool MT = false>
+__device__ __forceinline__ void w4_origin(int tile, int nwg, int tiles_m, int tiles_n, int& m0, int& n0,
+                                          const int* __restrict__ mt = nullptr, int mt_max = 0) {
   const int logical = xcd_remap(tile, nwg);
   const int group = logical / (WGROUP_M * tiles_n);
   const int first_m = group * WGROUP_M;
   const int gm = min(tiles_m - first_m, WGROUP_M);
   const int in_group = logical % (WGROUP_M * tiles_n);
-  m0 = (first_m + in_group % gm) * WBM;
+  int mi = first_m + in_group % gm;
+  if constexpr (MT) mi = (int)min((unsigned)mt[__builtin_amdgcn_readfirstlane(mi)], (unsigned)mt_max);
+  m0 = mi * WBM;
   n0 = (in_group / gm) * WBN;
 }
 
@@ -551,18 +557,26 @@ __device__ __forceinline__ void w4_origin(int tile, int nwg, int tiles_m, int ti
 // writes the fp32 partial tile of slab z to C + z * M * ldc (the consumer, e.g. add_partials_rmsnorm,
 // sums the slabs). For prefill shapes whose tile count fills only ~1.3 waves of the CUs (o_proj / down
 // at M ~ 5k: 336 tiles on 256 CUs), two slabs make 2.6 waves.
-template <int EPI, bool OUT_F32, bool KSPLIT = false>
+// MT: only the 256-row M-tiles listed in m_tiles[n_m_tiles] (strictly increasing) are computed: the work
+// items are n_m_tiles x tiles_n (x nsplit), numbered and grouped as above over the list, and every operand,
+// the residual, the output and the slabs are addressed in place by the real tile index, so a listed tile
+// is computed exactly as without a list and rows of unlisted tiles are neither read nor written. A block's
+// consecutive items may lie in non-adjacent M-tiles: the K-stream hand-over only ever uses the next
+// item's own offsets.
+template <int EPI, bool OUT_F32, bool KSPLIT = false, bool MT = false>
 __global__ __launch_bounds__(W4_THREADS, 1) void gemm_w4_kernel(const bf16_t* __restrict__ A, int lda,
                                                                 const bf16_t* __restrict__ B, int ldb, void* C,
                                                                 int ldc, const bf16_t* __restrict__ bias,
                                                                 const bf16_t* resid, int ldr, int M, int N, int K,
-                                                                int nsplit, RopeKV rk) {
+                                                                int nsplit, RopeKV rk,
+                                                                const int* __restrict__ m_tiles, int n_m_tiles) {
   __shared__ __attribute__((aligned(16))) char smem[W4_LDS];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wid >> 1, wc = wid & 1;
   const int fr = lane & 15, fh = lane >> 4;
-  const int tiles_m = (M + WBM - 1) / WBM, tiles_n = (N + WBN - 1) / WBN;
+  const int tiles_m = MT ? n_m_tiles : (M + WBM - 1) / WBM, tiles_n = (N + WBN - 1) / WBN;
+  const int mt_max = (M + WBM - 1) / WBM - 1;
   const int nwg = tiles_m * tiles_n;
   const int nwt = KSPLIT ? nwg * nsplit : nwg;  // work items
   const int nk = K / WBK;
@@ -581,11 +595,13 @@ __global__ __launch_bounds__(W4_THREADS, 1) void gemm_w4_kernel(const bf16_t* __
   // them after the epilogue instead.
   constexpr bool LATE_F0 = !(EPI == EPI_NONE || EPI == EPI_SILU_MUL || (EPI == EPI_RESID && !OUT_F32));
   static_assert(EPI != EPI_ROPE_KV || (!OUT_F32 && !KSPLIT), "rope epilogue: bf16 output, no split-K");
+  static_assert(!MT || EPI == EPI_NONE || ((EPI == EPI_RESID || EPI == EPI_SILU_MUL) && !OUT_F32 && !KSPLIT),
+                "M-tile list: none / residual / SiLU*up epilogues and the split-K slabs");
 
   int tile = blockIdx.x;
   int z = KSPLIT ? tile / nwg : 0;
   int m0, n0;
-  w4_origin(tile - z * nwg, nwg, tiles_m, tiles_n, m0, n0);
+  w4_origin<MT>(tile - z * nwg, nwg, tiles_m, tiles_n, m0, n0, m_tiles, mt_max);
   int off_a[8], off_b[8];
   w4_offsets<false>(lda, m0, M, wid, lane, off_a);
   w4_offsets<true>(ldb, n0, N, wid, lane, off_b);
@@ -635,7 +651,7 @@ __global__ __launch_bounds__(W4_THREADS, 1) void gemm_w4_kernel(const bf16_t* __
     int nm0, nn0;
     const int ntile = has_next ? next : tile;
     const int nz = KSPLIT ? ntile / nwg : 0;
-    w4_origin(ntile - nz * nwg, nwg, tiles_m, tiles_n, nm0, nn0);
+    w4_origin<MT>(ntile - nz * nwg, nwg, tiles_m, tiles_n, nm0, nn0, m_tiles, mt_max);
     {
       int ln;  // == lane; opaque so the lane-only offset math is not hoisted out of the loop
       asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
@@ -704,14 +720,33 @@ static int w4_grid(int nwg) {
   return (g_w4_grid == 0 || g_w4_grid >= nwg) ? nwg : g_w4_grid;
 }
 
+// the epilogues that take an M-tile list (bf16 output)
+constexpr bool w4_mt_epi(int e) { return e == EPI_NONE || e == EPI_RESID || e == EPI_SILU_MUL; }
+
 template <int EPI, bool F32>
 int launch_w4(const void* A, int lda, const void* B, int ldb, void* C, int ldc, const void* bias, const void* resid,
-              int ldr, int M, int N, int K, hipStream_t st) {
-  const int nwg = ((M + WBM - 1) / WBM) * ((N + WBN - 1) / WBN);
+              int ldr, int M, int N, int K, const int* m_tiles, int n_m_tiles, hipStream_t st) {
+  const int tiles_n = (N + WBN - 1) / WBN;
+  if (m_tiles) {
+    if constexpr (w4_mt_epi(EPI) && !F32) {
+      hipLaunchKernelGGL((gemm_w4_kernel<EPI, F32, false, true>), dim3(w4_grid(n_m_tiles * tiles_n)),
+                         dim3(W4_THREADS), 0, st, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, C, ldc,
+                         (const bf16_t*)bias, (const bf16_t*)resid, ldr, M, N, K, 1, RopeKV{}, m_tiles, n_m_tiles);
+      return (int)hipGetLastError();
+    } else {
+      return (int)hipErrorInvalidValue;
+    }
+  }
+  const int nwg = ((M + WBM - 1) / WBM) * tiles_n;
   hipLaunchKernelGGL((gemm_w4_kernel<EPI, F32>), dim3(w4_grid(nwg)), dim3(W4_THREADS), 0, st, (const bf16_t*)A, lda,
                      (const bf16_t*)B, ldb, C, ldc, (const bf16_t*)bias, (const bf16_t*)resid, ldr, M, N, K, 1,
-                     RopeKV{});
+                     RopeKV{}, nullptr, 0);
   return (int)hipGetLastError();
+}
+
+// an M-tile list is either absent (null) or holds 1 .. ceil(M / 256) entries
+static bool w4_mt_ok(const int* m_tiles, int n_m_tiles, int M) {
+  return !m_tiles || (n_m_tiles >= 1 && n_m_tiles <= (M + WBM - 1) / WBM);
 }
 
 }  // namespace
@@ -724,23 +759,28 @@ RAGK_API int ragk_gemm_w4_set_grid(int g) {
 }
 
 // N = output columns (for EPI_SILU_MUL the weight has 2N rows, N % 128 == 0). Requires K % 64 == 0 and
-// K >= 192 (three K-tiles per tile for the continuous ring).
+// K >= 192 (three K-tiles per tile for the continuous ring). m_tiles (device, optional): n_m_tiles strictly
+// increasing 256-row M-tile indices -- only those tiles' rows are computed (epilogues none / residual /
+// SiLU*up, bf16 output); null = every tile.
 RAGK_API int ragk_gemm_w4(const void* A, int lda, const void* B, int ldb, void* C, int ldc, const void* bias,
-                          const void* resid, int ldr, int M, int N, int K, int epi, int out_f32, hipStream_t st) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
+                          const void* resid, int ldr, int M, int N, int K, int epi, int out_f32, const int* m_tiles,
+                          int n_m_tiles, hipStream_t st) {
+  if (M <= 0 || N <= 0 || K <= 0 || (m_tiles && n_m_tiles == 0)) return 0;
+  if (!w4_mt_ok(m_tiles, n_m_tiles, M)) return (int)hipErrorInvalidValue;
   if (K % WBK != 0 || K / WBK < W4_MIN_KT) return (int)hipErrorInvalidValue;
   const long long rows_b = (epi == EPI_SILU_MUL) ? 2LL * N : (long long)N;
   if ((long long)M * lda * 2 >= (1LL << 31) || rows_b * ldb * 2 >= (1LL << 31))
     return (int)hipErrorInvalidValue;  // 32-bit buffer offsets
   if (epi == EPI_SILU_MUL) {
     if (N % 128 != 0 || out_f32) return (int)hipErrorInvalidValue;
-    return launch_w4<EPI_SILU_MUL, false>(A, lda, B, ldb, C, ldc, bias, resid, ldr, M, 2 * N, K, st);
+    return launch_w4<EPI_SILU_MUL, false>(A, lda, B, ldb, C, ldc, bias, resid, ldr, M, 2 * N, K, m_tiles, n_m_tiles,
+                                          st);
   }
   if (N % 8 != 0) return (int)hipErrorInvalidValue;
 #define RAGK_W4_CASE(E) \
   case E:               \
-    return out_f32 ? launch_w4<E, true>(A, lda, B, ldb, C, ldc, bias, resid, ldr, M, N, K, st) \
-                   : launch_w4<E, false>(A, lda, B, ldb, C, ldc, bias, resid, ldr, M, N, K, st);
+    return out_f32 ? launch_w4<E, true>(A, lda, B, ldb, C, ldc, bias, resid, ldr, M, N, K, m_tiles, n_m_tiles, st) \
+                   : launch_w4<E, false>(A, lda, B, ldb, C, ldc, bias, resid, ldr, M, N, K, m_tiles, n_m_tiles, st);
   switch (epi) {
     RAGK_W4_CASE(EPI_NONE)
     RAGK_W4_CASE(EPI_BIAS)
@@ -756,17 +796,26 @@ RAGK_API int ragk_gemm_w4(const void* A, int lda, const void* B, int ldb, void* 
 }
 
 // Split-K prefill GEMM into fp32 slabs: P[z][M][N] = A[:, z*Ks:(z+1)*Ks] . B[:, z*Ks:(z+1)*Ks]^T,
-// Ks = K / nsplit, one persistent launch over nsplit x tiles work items (see KSPLIT).
+// Ks = K / nsplit, one persistent launch over nsplit x tiles work items (see KSPLIT). m_tiles / n_m_tiles as
+// for ragk_gemm_w4: the slabs' rows of unlisted tiles are not written.
 RAGK_API int ragk_gemm_w4_splitk(const void* A, int lda, const void* B, int ldb, float* P, int M, int N, int K,
-                                 int nsplit, hipStream_t st) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
+                                 int nsplit, const int* m_tiles, int n_m_tiles, hipStream_t st) {
+  if (M <= 0 || N <= 0 || K <= 0 || (m_tiles && n_m_tiles == 0)) return 0;
+  if (!w4_mt_ok(m_tiles, n_m_tiles, M)) return (int)hipErrorInvalidValue;
   if (nsplit < 1 || K % nsplit || (K / nsplit) % WBK || (K / nsplit) / WBK < W4_MIN_KT || N % 8 || !P)
     return (int)hipErrorInvalidValue;
   if ((long long)M * lda * 2 >= (1LL << 31) || (long long)N * ldb * 2 >= (1LL << 31)) return (int)hipErrorInvalidValue;
+  if (m_tiles) {
+    const int nwt = n_m_tiles * ((N + WBN - 1) / WBN) * nsplit;
+    hipLaunchKernelGGL((gemm_w4_kernel<EPI_NONE, true, true, true>), dim3(w4_grid(nwt)), dim3(W4_THREADS), 0, st,
+                       (const bf16_t*)A, lda, (const bf16_t*)B, ldb, (void*)P, N, nullptr, nullptr, 0, M, N,
+                       K / nsplit, nsplit, RopeKV{}, m_tiles, n_m_tiles);
+    return (int)hipGetLastError();
+  }
   const int nwg = ((M + WBM - 1) / WBM) * ((N + WBN - 1) / WBN);
   hipLaunchKernelGGL((gemm_w4_kernel<EPI_NONE, true, true>), dim3(w4_grid(nwg * nsplit)), dim3(W4_THREADS), 0, st,
                      (const bf16_t*)A, lda, (const bf16_t*)B, ldb, (void*)P, N, nullptr, nullptr, 0, M, N, K / nsplit,
-                     nsplit, RopeKV{});
+                     nsplit, RopeKV{}, nullptr, 0);
   return (int)hipGetLastError();
 }
 
@@ -784,6 +833,6 @@ RAGK_API int ragk_gemm_w4_rope_kv(const void* A, int lda, const void* B, int ldb
   const int nwg = ((M + WBM - 1) / WBM) * (N / WBN);
   const RopeKV rk{pos, slot, cos_t, sin_t, (bf16_t*)kc, (bf16_t*)vc, Hq, Hkv, BS};
   hipLaunchKernelGGL((gemm_w4_kernel<EPI_ROPE_KV, false>), dim3(w4_grid(nwg)), dim3(W4_THREADS), 0, st,
-                     (const bf16_t*)A, lda, (const bf16_t*)B, ldb, C, ldc, nullptr, nullptr, 0, M, N, K, 1, rk);
+                     (const bf16_t*)A, lda, (const bf16_t*)B, ldb, C, ldc, nullptr, nullptr, 0, M, N, K, 1, rk, nullptr, 0);
   return (int)hipGetLastError();
 }

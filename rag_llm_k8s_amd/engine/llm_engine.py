@@ -514,16 +514,24 @@ class LLMEngine:
             if start + n == len(s.prompt) or (start + n == s.length and start >= len(s.prompt)):
                 out_rows.append(cu[-1] - 1)
                 out_seqs.append(s)
-        from ..ops.native import build_prefill_tiles
+        from ..ops.native import build_last_rows_lists, build_prefill_tiles
 
         m = self.model
         tiles = build_prefill_tiles(qlens, m.Hq, m.Hkv)
         meta = AttnMeta("prefill", self._h2d_i32(kvl), self._h2d_i32(bts), cu_q=self._h2d_i32(cu),
                         tiles=tiles.to(self.device), host_kv_lens=kvl, host_q_lens=qlens)
         ntok = cu[-1]
+        # the rows read after the last decoder layer (models/llama.py:_last_rows): with none (no prompt ends in
+        # this chunk) a model that cuts its last layer gets the empty list, any other the last row as before
+        cuts = getattr(m, "prefill_last_rows_enabled", None)
+        cuts = self.tp_size == 1 and cuts is not None and cuts()
+        m_tiles = None
+        if cuts and out_rows:
+            tl, mt = build_last_rows_lists(qlens, out_rows, m.Hq, m.Hkv, tiles=tiles)
+            meta.tiles_last, m_tiles = self._h2d_i32(tl.numpy()), self._h2d_i32(mt.numpy())
         inp = StepInput(self._h2d_i32(np.concatenate(ids)), self._h2d_i32(np.concatenate(pos)),
                         self._h2d_i32(np.concatenate(slots)), meta,
-                        self._h2d_i32(out_rows) if out_rows else self._h2d_i32([ntok - 1]))
+                        self._h2d_i32(out_rows if out_rows or cuts else [ntok - 1]), m_tiles=m_tiles)
         return inp, out_seqs, ntok
 
     @staticmethod

@@ -247,6 +247,10 @@ class StepInput:
     slots: torch.Tensor  # int32 [T]
     meta: AttnMeta
     logits_idx: Optional[torch.Tensor] = None  # int32 [n] rows that need logits (None = all)
+    # prefill, optional: unique(logits_idx // 256), strictly increasing int32 on the device -- the 256-row
+    # GEMM tiles the last decoder layer has to compute (ops/native.py:build_last_rows_lists, with
+    # meta.tiles_last); None = the last layer runs on every row
+    m_tiles: Optional[torch.Tensor] = None
     # asynchronous decode: carry[i] >= 0 -> ids[i] = carry_src[carry[i]] (previous step's sampled token,
     # resolved on the device by the embedding kernel)
     carry: Optional[torch.Tensor] = None
@@ -322,7 +326,34 @@ class LlamaModel:
     def _final(self, h, inp: StepInput):
         if inp.logits_idx is not None:
             h = self.be.gather_rows(h, inp.logits_idx)
+            if h.shape[0] == 0:
+                return h
         return self.be.rmsnorm(h, self.w.norm, self.cfg.rms_norm_eps)
+
+    @staticmethod
+    def prefill_last_rows_enabled():
+        """RAGK_PREFILL_LAST_ROWS=0 restores the full last layer of a prefill step (A/B switch)."""
+        return os.environ.get("RAGK_PREFILL_LAST_ROWS", "1") != "0"
+
+    def _last_rows(self, inp: StepInput, M):
+        """How the last decoder layer of this TP=1 prefill / mixed step may be cut down to the rows that are
+        read afterwards (logits_idx): None (run it on every row), "skip" (logits_idx is empty: only its
+        qkv projection / KV write runs) or "tiles" (attention on meta.tiles_last, o_proj / gate-up / down on
+        the 256-row tiles inp.m_tiles). "tiles" needs every one of those GEMMs on the kernel the full call
+        takes (be.m_tiles_ok: bf16 weights, native backend, the large-M route), so a listed tile is computed
+        by the same code in the same K order and the returned rows are bit-identical."""
+        if (self.comm is not None or inp.meta is None or inp.meta.kind == "decode" or inp.logits_idx is None
+                or not self.prefill_last_rows_enabled()):
+            return None
+        if inp.logits_idx.numel() == 0:
+            return "skip"
+        if inp.m_tiles is None or inp.meta.tiles_last is None:
+            return None
+        L, be = self.w.layers[-1], self.be
+        if not (be.m_tiles_ok(M, L["wo"], "resid") and be.m_tiles_ok(M, L["wgu"], "silu_mul")
+                and be.m_tiles_ok(M, L["wdown"], "resid")):
+            return None
+        return "tiles"
 
     def _tp(self):
         return self.comm is not None and self.comm.size > 1
@@ -407,7 +438,13 @@ class LlamaModel:
         return xn
 
     def hidden_states(self, inp: StepInput):
-        """Run the decoder stack; returns the final-norm'ed rows selected by logits_idx."""
+        """Run the decoder stack; returns the final-norm'ed rows selected by logits_idx.
+
+        Only those rows are defined: on a TP=1 prefill / mixed step the last layer computes nothing else
+        (_last_rows), so outside the 256-row tiles (GEMMs) and 64-query blocks (attention) that hold a row of
+        logits_idx the step's internal buffers (attn, the activations, the split-K slabs, h) keep stale or
+        unspecified values after the last layer. Nothing reads them: every path gathers logits_idx before
+        it returns, and every layer's K/V rows are written for all tokens."""
         be, w = self.be, self.w
         h = be.embed(inp.ids, w.embed, carry=inp.carry, prev=inp.carry_src)
         if self._decode_part_ok(inp, h):
@@ -418,12 +455,34 @@ class LlamaModel:
             ns = (be.prefill_nsplit(h.shape[0], L0["wo"]), be.prefill_nsplit(h.shape[0], L0["wdown"]))
             if max(ns) > 1:
                 return self.hidden_states_splitk(inp, h, attn, *ns)
+        last = self._last_rows(inp, h.shape[0])
         for li, L in enumerate(w.layers):
+            if last is not None and li + 1 == len(w.layers):
+                self._last_layer_rows(li, L, h, inp, attn, last)
+                break
             self._attn_block(li, L, h, inp, attn)
             self._allreduce(h)
             self._mlp_block(L, h)
             self._allreduce(h)
         return self._final(h, inp)
+
+    def _last_layer_rows(self, li, L, h, inp: StepInput, attn, mode):
+        """The last decoder layer of a TP=1 prefill step (see _last_rows): the input norm and the qkv
+        projection run on every row (every row's K/V reaches the cache); attention, o_proj, gate/up and down
+        only where a row of logits_idx lies. The norms stay full-height (row-independent, cheap)."""
+        be, c = self.be, self.cfg
+        Hq, Hkv, D = self.Hq, self.Hkv, self.D
+        kc, vc = self.kv_cache[li]
+        xn = be.rmsnorm(h, L["ln_in"], c.rms_norm_eps)
+        qkv = be.gemm_rope_kv(xn, L["wqkv"], inp.positions, self.cos, self.sin, inp.slots, kc, vc, Hq, Hkv, D)
+        if mode == "skip":
+            return
+        mt = inp.m_tiles
+        be.attn_prefill(qkv, kc, vc, inp.meta, attn, Hq, Hkv, D, tiles=inp.meta.tiles_last)
+        be.gemm(attn, L["wo"], resid=h, epi="resid", out=h, m_tiles=mt)
+        xn = be.rmsnorm(h, L["ln_post"], c.rms_norm_eps)
+        a = be.gemm(xn, L["wgu"], epi="silu_mul", m_tiles=mt)
+        be.gemm(a, L["wdown"], resid=h, epi="resid", out=h, m_tiles=mt)
 
     def hidden_states_splitk(self, inp: StepInput, h, attn, ns_o, ns_d):
         """TP=1 prefill of a step too small to fill the CUs with 256x256 output tiles (a single ~5k-token
@@ -434,22 +493,31 @@ class LlamaModel:
         be, w, c = self.be, self.w, self.cfg
         Hq, Hkv, D = self.Hq, self.Hkv, self.D
         layers = w.layers
+        last = self._last_rows(inp, h.shape[0])
         xn = be.rmsnorm(h, layers[0]["ln_in"], c.rms_norm_eps)
         for li, L in enumerate(layers):
             kc, vc = self.kv_cache[li]
+            # the last layer only where a row of logits_idx lies (_last_rows): its GEMM row tiles / attention
+            # blocks; the slab counts stay those of the full M, so the summation order does too
+            cut = last if li + 1 == len(layers) else None
+            rows = {"m_tiles": inp.m_tiles} if cut == "tiles" else {}
+            blocks = {"tiles": inp.meta.tiles_last} if cut == "tiles" else {}
             qkv = be.gemm_rope_kv(xn, L["wqkv"], inp.positions, self.cos, self.sin, inp.slots, kc, vc, Hq, Hkv, D)
-            be.attn_prefill(qkv, kc, vc, inp.meta, attn, Hq, Hkv, D)
+            if cut == "skip":
+                return h.new_empty((0, h.shape[1]))
+            be.attn_prefill(qkv, kc, vc, inp.meta, attn, Hq, Hkv, D, **blocks)
             if ns_o > 1:
-                xn = be.add_partials_rmsnorm(be.gemm_splitk(attn, L["wo"], ns_o), h, L["ln_post"], c.rms_norm_eps)
+                xn = be.add_partials_rmsnorm(be.gemm_splitk(attn, L["wo"], ns_o, **rows), h, L["ln_post"],
+                                             c.rms_norm_eps)
             else:
-                be.gemm(attn, L["wo"], resid=h, epi="resid", out=h)
+                be.gemm(attn, L["wo"], resid=h, epi="resid", out=h, **rows)
                 xn = be.rmsnorm(h, L["ln_post"], c.rms_norm_eps)
-            a = be.gemm(xn, L["wgu"], epi="silu_mul")
+            a = be.gemm(xn, L["wgu"], epi="silu_mul", **rows)
             nxt = layers[li + 1]["ln_in"] if li + 1 < len(layers) else w.norm
             if ns_d > 1:
-                xn = be.add_partials_rmsnorm(be.gemm_splitk(a, L["wdown"], ns_d), h, nxt, c.rms_norm_eps)
+                xn = be.add_partials_rmsnorm(be.gemm_splitk(a, L["wdown"], ns_d, **rows), h, nxt, c.rms_norm_eps)
             else:
-                be.gemm(a, L["wdown"], resid=h, epi="resid", out=h)
+                be.gemm(a, L["wdown"], resid=h, epi="resid", out=h, **rows)
                 xn = be.rmsnorm(h, nxt, c.rms_norm_eps)
         if inp.logits_idx is not None:
             xn = be.gather_rows(xn, inp.logits_idx)

@@ -34,6 +34,9 @@ class AttnMeta:
     block_tables: torch.Tensor  # int32 [S, maxb]
     cu_q: Optional[torch.Tensor] = None  # int32 [S+1] (prefill)
     tiles: Optional[torch.Tensor] = None  # int32 [n,2] (prefill)
+    # prefill, optional: the entries of `tiles` whose query block holds a row of the step's logits_idx (the
+    # last decoder layer's attention needs no others; ops/native.py:build_last_rows_lists)
+    tiles_last: Optional[torch.Tensor] = None
     part_tiles: int = 4  # decode split-K
     max_parts: int = 1
     ws_o: Optional[torch.Tensor] = None
@@ -209,6 +212,10 @@ class TorchBackend:
     def prefill_nsplit(self, M, w):
         return 1
 
+    def m_tiles_ok(self, M, w, epi="none"):
+        """Whether gemm(..., m_tiles=) computes listed row tiles bit-identically to the full call."""
+        return False
+
     def attn_decode(self, q, kc, vc, meta: AttnMeta, out, Hq, Hkv, D):
         B = q.shape[0]
         cu = torch.arange(B + 1, dtype=torch.int32)
@@ -277,12 +284,20 @@ class NativeBackend(TorchBackend):
         self.n = native
         native._lib.lib()  # fail loudly now if the gfx950 library is missing
 
-    def gemm(self, x, w, bias=None, resid=None, epi="none", out=None, out_f32=False):
+    def gemm(self, x, w, bias=None, resid=None, epi="none", out=None, out_f32=False, m_tiles=None):
+        if m_tiles is not None and isinstance(w, _QUANT):
+            raise ValueError("m_tiles: bf16 weights only")
         if isinstance(w, Fp8Weight):
             return self.n.gemm_fp8(x, w, bias=bias, resid=resid, epi=epi, out=out, out_f32=out_f32)
         if isinstance(w, Mxfp4Weight):
             return self.n.gemm_mxfp4(x, w, bias=bias, resid=resid, epi=epi, out=out, out_f32=out_f32)
-        return self.n.gemm(x, w, bias=bias, resid=resid, epi=epi, out=out, out_f32=out_f32)
+        return self.n.gemm(x, w, bias=bias, resid=resid, epi=epi, out=out, out_f32=out_f32, m_tiles=m_tiles)
+
+    def m_tiles_ok(self, M, w, epi="none"):
+        if isinstance(w, _QUANT):
+            return False
+        N = w.shape[0] // 2 if epi == "silu_mul" else w.shape[0]
+        return self.n.gemm_m_tiles_ok(M, N, w.shape[1], epi, ldb=w.stride(0))
 
     def rmsnorm(self, x, w, eps, out=None):
         return self.n.rmsnorm(x, w, eps, out=out)
@@ -352,9 +367,10 @@ class NativeBackend(TorchBackend):
     def rope_kv_partials(self, P, q_out, positions, cos_t, sin_t, slots, kc, vc, Hq, Hkv, D):
         self.n.rope_kv_partials(P, q_out, positions, cos_t, sin_t, slots, kc, vc, Hq, Hkv, D)
 
-    def attn_prefill(self, q, kc, vc, meta: AttnMeta, out, Hq, Hkv, D):
-        return self.n.attn_prefill(q, kc, vc, meta.cu_q, meta.kv_lens, meta.tiles, out, Hq, Hkv, D, causal=True,
-                                   paged=True, block_tables=meta.block_tables)
+    def attn_prefill(self, q, kc, vc, meta: AttnMeta, out, Hq, Hkv, D, tiles=None):
+        """tiles: a sub-list of meta.tiles -- only those query blocks' rows of `out` are written."""
+        return self.n.attn_prefill(q, kc, vc, meta.cu_q, meta.kv_lens, meta.tiles if tiles is None else tiles, out,
+                                   Hq, Hkv, D, causal=True, paged=True, block_tables=meta.block_tables)
 
     def attn_decode_rope(self, P, positions, cos_t, sin_t, slots, kc, vc, meta: AttnMeta, out, Hq, Hkv, D,
                          defer_merge=False):
@@ -367,8 +383,8 @@ class NativeBackend(TorchBackend):
             return 1
         return self.n.prefill_nsplit(M, w.shape[0], w.shape[1])
 
-    def gemm_splitk(self, x, w, nsplit):
-        return self.n.gemm_splitk(x, w, nsplit)
+    def gemm_splitk(self, x, w, nsplit, m_tiles=None):
+        return self.n.gemm_splitk(x, w, nsplit, m_tiles=m_tiles)
 
     def part_merge_ok(self, M, meta: AttnMeta, w, Hq, D):
         return (self.enable_part and D == 128 and not isinstance(w, Mxfp4Weight)

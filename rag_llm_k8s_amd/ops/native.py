@@ -184,9 +184,31 @@ def _gemm_blas(x, w, resid, out, epi):
     return torch.mm(x, w.t(), out=out)
 
 
-def gemm(x, w, bias=None, resid=None, epi="none", out=None, out_f32=False, path=None):
+def _m_tiles_arg(m_tiles, M, dev):
+    """(pointer, count) of an M-tile list: int32 on the launch device, 0 .. ceil(M / 256) entries (strictly
+    increasing tile indices below ceil(M / 256): the caller's contract, the kernel clamps)."""
+    _req(isinstance(m_tiles, torch.Tensor) and m_tiles.dtype == torch.int32 and m_tiles.dim() == 1
+         and m_tiles.is_contiguous() and m_tiles.is_cuda and m_tiles.device == dev, "m_tiles: int32 [n] on the GPU")
+    _req(m_tiles.numel() <= -(-M // 256), "m_tiles: more entries than 256-row tiles")
+    return m_tiles.data_ptr(), m_tiles.numel()
+
+
+def gemm_m_tiles_ok(M, N, K, epi="none", lda=None, ldb=None):
+    """Whether gemm's default route for this shape is gemm_w4, i.e. whether gemm(..., m_tiles=) computes the
+    listed tiles with the very kernel (tiles, K order) the call without a list runs."""
+    if epi not in ("none", "resid", "silu_mul") or PREFILL_BLAS != "none" or not use_pp(M, N, K, epi):
+        return False
+    rows = 2 * N if epi == "silu_mul" else N
+    return (lda or K) * M * 2 < 2 ** 31 and (ldb or K) * rows * 2 < 2 ** 31
+
+
+def gemm(x, w, bias=None, resid=None, epi="none", out=None, out_f32=False, path=None, m_tiles=None):
     """out[M,N] = epi(x[M,K] @ w[N,K]^T). For epi='silu_mul', w is the packed
-    gate/up weight [2N, K] (see reference.pack_gate_up) and out has N columns."""
+    gate/up weight [2N, K] (see reference.pack_gate_up) and out has N columns.
+
+    m_tiles (int32 device tensor, strictly increasing 256-row tile indices): compute only the rows of those
+    tiles, in place; the other rows of x and resid are not read and those of out not written. Forces the
+    gemm_w4 kernel (epi none / resid / silu_mul, bf16 output) and raises where it cannot take the operands."""
     _bf16_2d(x, "x")
     _bf16_2d(w, "w")
     M, K = x.shape
@@ -215,6 +237,17 @@ def gemm(x, w, bias=None, resid=None, epi="none", out=None, out_f32=False, path=
     _al16(w, "w")
     L = _lib.lib()
     ldr = resid.stride(0) if resid is not None else 0
+    mt_ptr, mt_n = None, 0
+    if m_tiles is not None:
+        _req(path in (None, 6), "m_tiles: only the gemm_w4 path takes an M-tile list")
+        _req(epi in ("none", "resid", "silu_mul") and not out_f32, "m_tiles: epi none / resid / silu_mul, bf16 out")
+        _req(K % 64 == 0 and K >= 192 and (N % 128 == 0 if epi == "silu_mul" else N % 8 == 0), "m_tiles: gemm_w4 shape")
+        # gemm_w4 addresses operands with 32-bit buffer offsets
+        _req(x.stride(0) * M * 2 < 2 ** 31 and w.stride(0) * w.shape[0] * 2 < 2 ** 31, "m_tiles: operand past 2 GiB")
+        mt_ptr, mt_n = _m_tiles_arg(m_tiles, M, x.device)
+        if mt_n == 0:
+            return out
+        path = 6
     if (path is None and PREFILL_BLAS != "none" and not out_f32 and bias is None and use_pp(M, N, K, epi)
             and ((epi == "none" and PREFILL_BLAS in ("plain", "all"))
                  or (epi == "resid" and PREFILL_BLAS in ("resid", "all")))):
@@ -254,7 +287,7 @@ def gemm(x, w, bias=None, resid=None, epi="none", out=None, out_f32=False, path=
                             ptr(bias), ptr(resid), ldr, M, N, K, e, int(out_f32), stream_ptr())
     elif path == 6:
         rc = L.ragk_gemm_w4(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), out.stride(0),
-                            ptr(bias), ptr(resid), ldr, M, N, K, e, int(out_f32), stream_ptr())
+                            ptr(bias), ptr(resid), ldr, M, N, K, e, int(out_f32), mt_ptr, mt_n, stream_ptr())
     elif path is None:
         rc = L.ragk_gemm(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), out.stride(0),
                          ptr(bias), ptr(resid), ldr, M, N, K, e, int(out_f32), stream_ptr())
@@ -434,9 +467,10 @@ def prefill_nsplit(M, N, K):
     return best_s
 
 
-def gemm_splitk(x, w, nsplit, out=None):
+def gemm_splitk(x, w, nsplit, out=None, m_tiles=None):
     """fp32 split-K slabs P[nsplit, M, N] with P.sum(0) = x @ w^T, one persistent gemm_w4 launch
-    (csrc/kernels/gemm_w4.hip KSPLIT); consumed by add_partials_rmsnorm (residual add + norm)."""
+    (csrc/kernels/gemm_w4.hip KSPLIT); consumed by add_partials_rmsnorm (residual add + norm).
+    m_tiles: as for gemm -- only the listed 256-row tiles' rows of every slab are written."""
     _bf16_2d(x, "x")
     _bf16_2d(w, "w")
     M, K = x.shape
@@ -448,8 +482,11 @@ def gemm_splitk(x, w, nsplit, out=None):
          and out.data_ptr() % 16 == 0, "gemm_splitk out: contiguous fp32 slabs, 16-byte aligned")
     _al16(x, "x")  # buffer LDS-DMA operands, 16-byte slab stores
     _al16(w, "w")
+    mt_ptr, mt_n = _m_tiles_arg(m_tiles, M, x.device) if m_tiles is not None else (None, 0)
+    if m_tiles is not None and mt_n == 0:
+        return out
     check(_lib.lib().ragk_gemm_w4_splitk(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), M, N, K,
-                                         nsplit, stream_ptr()), "ragk_gemm_w4_splitk")
+                                         nsplit, mt_ptr, mt_n, stream_ptr()), "ragk_gemm_w4_splitk")
     return out
 
 
@@ -1122,6 +1159,34 @@ def build_prefill_tiles(q_lens, Hq, Hkv):
     q0 = (np.arange(int(nt.sum())) - first) * qt
     order = np.argsort(-q0, kind="stable")
     return torch.from_numpy(np.stack([seq[order], q0[order]], 1).astype(np.int32)).reshape(-1, 2)
+
+
+M_TILE_ROWS = 256  # gemm_w4's output tile height: the unit of gemm(..., m_tiles=)
+
+
+def build_last_rows_lists(q_lens, rows, Hq, Hkv, tiles=None):
+    """What the last decoder layer of a prefill step needs when only the packed rows `rows` (the step's
+    logits_idx, host ints) are read afterwards: (tiles_last, m_tiles), both host int32 tensors.
+    tiles_last: the entries of the (seq, q_start) attention work list (`tiles`, default
+    build_prefill_tiles(q_lens)) whose query block holds one of the rows, in the list's order.
+    m_tiles: the strictly increasing 256-row tile indices unique(rows // 256) for gemm(..., m_tiles=)."""
+    import numpy as np
+
+    qt = prefill_qtile(Hq, Hkv)
+    if tiles is None:
+        tiles = build_prefill_tiles(q_lens, Hq, Hkv)
+    t = tiles.numpy().reshape(-1, 2).astype(np.int64)
+    ql = np.asarray(q_lens, dtype=np.int64)
+    cu = np.concatenate([[0], np.cumsum(ql)])
+    r = np.unique(np.asarray(rows, dtype=np.int64).reshape(-1))
+    if r.size and (r[0] < 0 or r[-1] >= cu[-1]):
+        raise ValueError("build_last_rows_lists: row outside the packed step")
+    lo = cu[t[:, 0]] + t[:, 1]  # first / one-past-last packed row of every query block
+    hi = np.minimum(lo + qt, cu[t[:, 0] + 1])
+    keep = np.searchsorted(r, lo, side="left") < np.searchsorted(r, hi, side="left")
+    tiles_last = torch.from_numpy(np.ascontiguousarray(t[keep]).astype(np.int32)).reshape(-1, 2)
+    m_tiles = torch.from_numpy(np.unique(r // M_TILE_ROWS).astype(np.int32))
+    return tiles_last, m_tiles
 
 
 def attn_prefill(q, k, v, cu_q, kv_lens, tiles, out, Hq, Hkv, D, causal=True, paged=True, block_tables=None,
