@@ -42,6 +42,11 @@ class RagConfig:
     temperature: float = 0.7
     top_p: float = 0.9
     top_k: int = 50
+    # history-dependent logit processors (transformers' generate() arguments of the same names); the defaults
+    # mean off. A /generate request may override them with JSON fields of the same names.
+    repetition_penalty: float = 1.0
+    no_repeat_ngram_size: int = 0
+    min_new_tokens: int = 0
     do_sample: Optional[bool] = None  # None -> generation_config.json (reference: model.generate defaults)
     seed: int = 0
     tp_size: int = 1
@@ -89,6 +94,8 @@ class RagConfig:
             "RETRIEVE_K": ("retrieve_k", int), "CONTEXT_K": ("context_k", int), "CHUNK_WORDS": ("chunk_words", int),
             "CHUNK_OVERLAP": ("chunk_overlap", int), "MAX_NEW_TOKENS": ("max_new_tokens", int),
             "TEMPERATURE": ("temperature", float), "TOP_P": ("top_p", float), "TOP_K": ("top_k", int),
+            "REPETITION_PENALTY": ("repetition_penalty", float), "NO_REPEAT_NGRAM_SIZE": ("no_repeat_ngram_size", int),
+            "MIN_NEW_TOKENS": ("min_new_tokens", int),
             "SEED": ("seed", int), "TP_SIZE": ("tp_size", int), "DTYPE": ("dtype", str), "DEVICE": ("device", str),
             "INDEX_TYPE": ("index_type", str), "IVF_NLIST": ("ivf_nlist", int), "IVF_NPROBE": ("ivf_nprobe", int),
             "REINGEST_APPEND": ("reingest_append", bool), "MAX_BATCH": ("max_batch", int),

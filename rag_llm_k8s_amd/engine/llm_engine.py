@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import itertools
 import logging
+import math
 import os
 import threading
 import time
@@ -44,6 +45,11 @@ from .kv_manager import BLOCK, make_block_manager
 SMALL_BATCH_TOPK_MAX_B = 64
 SMALL_BATCH_TOPK_CHUNK = 4096
 
+# history-dependent logit processors (csrc/kernels/logits_proc.hip): widest n-gram ban, and the width of the
+# per-row ban id table (the ids a request stops on, banned while it has fewer than min_new_tokens tokens)
+NGRAM_MAX = 8
+BAN_IDS_MAX = 16
+
 log = logging.getLogger(__name__)
 
 
@@ -57,6 +63,15 @@ class SamplingParams:
     seed: Optional[int] = None
     stop_token_ids: tuple = ()
     ignore_eos: bool = False  # benchmark mode: always generate max_new_tokens
+    # history-dependent logit processors, transformers' semantics over prompt + generated tokens; the
+    # defaults mean off, and a request that enables none runs exactly the launches it ran without them
+    repetition_penalty: float = 1.0  # RepetitionPenaltyLogitsProcessor
+    no_repeat_ngram_size: int = 0  # NoRepeatNGramLogitsProcessor, 0..NGRAM_MAX
+    min_new_tokens: int = 0  # MinNewTokensLengthLogitsProcessor over eos + stop_token_ids
+
+    def uses_processors(self) -> bool:
+        return (self.repetition_penalty != 1.0 or self.no_repeat_ngram_size > 0
+                or (self.min_new_tokens > 0 and not self.ignore_eos))
 
 
 WAITING, RUNNING, FINISHED = 0, 1, 2
@@ -84,6 +99,7 @@ class Sequence:
         self.finish_reason = None
         self.done = threading.Event()
         self.user = None  # opaque payload for the caller
+        self.hist_row = -1  # row of the engine's device token history (-1: no logit processors)
 
     @property
     def length(self):
@@ -169,6 +185,14 @@ class LLMEngine:
         # (any bucket) reads its carried ids from it inside the embedding kernel (packed "carry" map)
         self._tok_out = torch.zeros(max(self.buckets + [max_batch, 1]), dtype=torch.int32,
                                     device=self.device) if self.is_cuda else None
+        # Device token history of the logit processors: hist[row][position] = token at that position, one row
+        # per sequence that enables a processor, allocated at the first such request (_ensure_hist). Every
+        # write is idempotent, so discarded / recomputed steps rewrite the same cells; a finished sequence's
+        # row is released with the same deferral as its KV blocks (_hist_after).
+        self._hist = None
+        self._hist_free = None
+        self._hist_after = []
+        self.stats["logit_proc_steps"] = 0
 
     # ------------------------------------------------------------------ requests
     def add_request(self, prompt_ids, params: SamplingParams, seed: Optional[int] = None) -> Sequence:
@@ -177,6 +201,7 @@ class LLMEngine:
         if len(prompt_ids) + params.max_new_tokens > self.max_model_len:
             raise ValueError("prompt (%d) + max_new_tokens (%d) exceeds max_model_len %d"
                              % (len(prompt_ids), params.max_new_tokens, self.max_model_len))
+        self.check_params(params)
         s = Sequence(prompt_ids, params, seed if seed is not None else (params.seed if params.seed is not None
                                                                         else int(time.time_ns() & 0xFFFFFFFF)))
         with self.lock:
@@ -189,7 +214,89 @@ class LLMEngine:
         if len(prompt_ids) + params.max_new_tokens > self.max_model_len:
             raise ValueError("prompt (%d) + max_new_tokens (%d) exceeds max_model_len %d"
                              % (len(prompt_ids), params.max_new_tokens, self.max_model_len))
+        self.check_params(params)
         return Sequence(prompt_ids, params, seed)
+
+    def _stop_ids(self, p):
+        """The ids a request stops on (what min_new_tokens bans): the engine's eos set + its stop_token_ids."""
+        return sorted(self.eos | set(int(t) for t in p.stop_token_ids))
+
+    def check_params(self, p: SamplingParams):
+        rp, n, m = p.repetition_penalty, p.no_repeat_ngram_size, p.min_new_tokens
+        if isinstance(rp, bool) or not isinstance(rp, (int, float)) or not math.isfinite(rp) or rp <= 0:
+            raise ValueError("repetition_penalty must be a finite number > 0 (got %r)" % (rp,))
+        if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= NGRAM_MAX:
+            raise ValueError("no_repeat_ngram_size must be an integer in 0..%d (got %r)" % (NGRAM_MAX, n))
+        if isinstance(m, bool) or not isinstance(m, int) or not 0 <= m <= p.max_new_tokens:
+            raise ValueError("min_new_tokens must be an integer in 0..max_new_tokens=%d (got %r)"
+                             % (p.max_new_tokens, m))
+        if m > 0 and not p.ignore_eos and len(self._stop_ids(p)) > BAN_IDS_MAX:
+            raise ValueError("min_new_tokens: at most %d eos + stop ids" % BAN_IDS_MAX)
+        if p.uses_processors() and self.is_cuda:
+            from ..ops.native import logits_proc_max_hist
+            if self.max_model_len > logits_proc_max_hist():
+                raise ValueError("logit processors: max_model_len %d exceeds the %d history entries the kernel "
+                                 "stages" % (self.max_model_len, logits_proc_max_hist()))
+
+    # ------------------------------------------------------------------ token history (logit processors)
+    def _ensure_hist(self):
+        if self._hist is None:
+            self._hist = torch.zeros((max(1, self.max_batch), self.max_model_len), dtype=torch.int32,
+                                     device=self.device)
+            self._hist_free = list(range(self._hist.shape[0] - 1, -1, -1))
+
+    def _free_deferred(self):
+        """The in-flight step that could still write them has completed: release the KV blocks and history
+        rows of the sequences that finished while it ran."""
+        for sid in self._free_after:
+            self.bm.free(sid)
+        self._free_after = []
+        if self._hist_after:
+            self._hist_free.extend(self._hist_after)
+            self._hist_after = []
+
+    def _proc_host(self, seqs, gen, pad_to=None):
+        """int32 [(4 + BAN_IDS_MAX) n] = history rows | penalty (f32) | n-gram size | ban count | ban ids [n, W].
+        gen[i]: tokens sequence i has generated before the one being sampled. Plain and padded rows: row -1."""
+        n = pad_to or len(seqs)
+        rows = np.full(n, -1, dtype=np.int32)
+        pen = np.ones(n, dtype=np.float32)
+        ng = np.zeros(n, dtype=np.int32)
+        cnt = np.zeros(n, dtype=np.int32)
+        ban = np.zeros((n, BAN_IDS_MAX), dtype=np.int32)
+        for i, s in enumerate(seqs):
+            if s.hist_row < 0:
+                continue
+            p = s.params
+            rows[i], pen[i], ng[i] = s.hist_row, p.repetition_penalty, p.no_repeat_ngram_size
+            if not p.ignore_eos and gen[i] < p.min_new_tokens:
+                stop = self._stop_ids(p)
+                cnt[i] = len(stop)
+                ban[i, :len(stop)] = stop
+        return np.concatenate([rows, pen.view(np.int32), ng, cnt, ban.reshape(-1)])
+
+    @staticmethod
+    def _proc_views(buf, n):
+        return dict(rows=buf[0:n], penalty=buf[n:2 * n].view(torch.float32), ngram=buf[2 * n:3 * n],
+                    ban_count=buf[3 * n:4 * n], ban_ids=buf[4 * n:(4 + BAN_IDS_MAX) * n].view(n, BAN_IDS_MAX))
+
+    def _proc_tensors(self, seqs, pos, gen, ids=None):
+        """Processor argument block of an eager sampling call (None if no row of it has a history row).
+        pos[i]: position of sequence i's last token (history length - 1); ids: decode input ids, stored into
+        the history by the kernel, or None when the history is already complete (prefill's sampled rows)."""
+        if not any(s.hist_row >= 0 for s in seqs):
+            return None
+        n = len(seqs)
+        buf = self._h2d_i32(np.concatenate([self._proc_host(seqs, gen), np.asarray(pos, dtype=np.int32)]))
+        proc = self._proc_views(buf, n)
+        proc["pos"] = buf[(4 + BAN_IDS_MAX) * n:(5 + BAN_IDS_MAX) * n]
+        proc["ids"] = ids
+        return proc
+
+    def _apply_processors(self, lg, proc):
+        be = self.model.be
+        be.logits_process(lg, self.model.w.vocab_offset, proc["ids"], proc["rows"], proc["pos"], self._hist,
+                          proc["penalty"], proc["ngram"], proc["ban_ids"], proc["ban_count"])
 
     def add_sequence(self, s: Sequence):
         with self.lock:
@@ -220,6 +327,14 @@ class LLMEngine:
                 need = len(s.prompt) + s.params.max_new_tokens
                 if not self.bm.can_allocate(s.id, need):
                     break
+                if s.params.uses_processors():
+                    self._ensure_hist()
+                    # one row per running sequence (max_batch rows, len(running) < max_batch here): none free
+                    # means finished sequences' rows are still held for the in-flight step; the next collect
+                    # releases them
+                    if not self._hist_free:
+                        break
+                    s.hist_row = self._hist_free.pop()
                 self.waiting.popleft()
                 self.bm.ensure(s.id, need)
                 s.status = RUNNING
@@ -342,10 +457,13 @@ class LLMEngine:
         s.status = FINISHED
         s.finish_reason = reason
         s.t_done = time.perf_counter()
-        if defer_free:  # a step still in flight writes this sequence's KV row
+        if defer_free:  # a step still in flight writes this sequence's KV row (and its history row)
             self._free_after.append(s.id)
         else:
             self.bm.free(s.id)
+        if s.hist_row >= 0:
+            (self._hist_after if defer_free else self._hist_free).append(s.hist_row)
+            s.hist_row = -1
         self.running.remove(s)
         s.done.set()
 
@@ -401,12 +519,15 @@ class LLMEngine:
             self._warned_topk = True
         return bad
 
-    def _sample_full_vocab(self, logits, seqs):
+    def _sample_full_vocab(self, logits, seqs, proc=None):
         """Exact temperature -> top-k (if 0 < top_k) -> top-p -> multinomial over the whole vocabulary
         (transformers' LogitsProcessor order, [dep] generation/utils.py:1311-1322). Under TP the vocab
         shards are all-gathered first. Uniforms come from torch.Generator(seed * 1000003 + step), as in
-        the torch backend's sampler."""
+        the torch backend's sampler. `proc`: the logit processors' argument block (_proc_tensors), applied
+        first, on this rank's shard."""
         w = self.model.w
+        if proc is not None:
+            self._apply_processors(logits[:, :w.vocab_valid] if w.vocab_valid < logits.shape[1] else logits, proc)
         lg = logits[:, :w.vocab_valid].float().contiguous()
         if self.tp_size > 1:
             import torch.distributed as dist
@@ -449,10 +570,14 @@ class LLMEngine:
             toks.append(int(order[j]))
         return toks
 
-    def _sample_rows(self, logits, temps, ks, ps, seeds, steps, out=None):
+    def _sample_rows(self, logits, temps, ks, ps, seeds, steps, out=None, proc=None):
+        """`proc` (optional): the logit processors' argument block; their kernel then runs in place on the
+        logits before the candidate top-k (temperature / top-k / top-p follow, as in transformers)."""
         be = self.model.be
         w = self.model.w
         lg = logits[:, :w.vocab_valid] if w.vocab_valid < logits.shape[1] else logits
+        if proc is not None:
+            self._apply_processors(lg, proc)
         # chunk count from the padded shard width so every TP rank gathers equal-sized lists,
         # and all ranks' candidates together fit the sampler's 2048-entry merge
         from ..ops.native import topk_chunks
@@ -532,6 +657,11 @@ class LLMEngine:
         inp = StepInput(self._h2d_i32(np.concatenate(ids)), self._h2d_i32(np.concatenate(pos)),
                         self._h2d_i32(np.concatenate(slots)), meta,
                         self._h2d_i32(out_rows if out_rows or cuts else [ntok - 1]), m_tiles=m_tiles)
+        if self._hist is not None and any(s.hist_row >= 0 for s, _, _ in chunks):
+            # the step's tokens enter the history of the sequences with logit processors: one scatter launch
+            # (per-token history row, -1 = skip); a chunked prompt fills its row chunk by chunk
+            hrows = np.concatenate([np.full(n, s.hist_row, dtype=np.int32) for s, _, n in chunks])
+            m.be.hist_write(inp.ids, self._h2d_i32(hrows), inp.positions, self._hist)
         return inp, out_seqs, ntok
 
     @staticmethod
@@ -573,10 +703,16 @@ class LLMEngine:
             if logits is None:
                 m.hidden_states(inp)
         finished = []
+        # logit processors of the sampled rows: their history (prompt, or prompt + generated for a mixed
+        # step's decode rows) was completed by this step's scatter
+        proc = self._proc_tensors(out_seqs, [s.length - 1 for s in out_seqs], [len(s.out) for s in out_seqs]) \
+            if out_seqs else None
+        if proc is not None:
+            self.stats["logit_proc_steps"] += 1
         if out_seqs and self._needs_full_vocab(out_seqs):
-            tok = self._sample_full_vocab(logits, out_seqs)
+            tok = self._sample_full_vocab(logits, out_seqs, proc=proc)
         elif out_seqs:
-            tok = self._sample_rows(logits, *self._sampling_tensors(out_seqs)).cpu().tolist()
+            tok = self._sample_rows(logits, *self._sampling_tensors(out_seqs), proc=proc).cpu().tolist()
         else:
             tok = []
             if self.is_cuda:
@@ -632,9 +768,14 @@ class LLMEngine:
             kvl[:n] = p + 1
         return out
 
-    def _decode_graph(self, B):
-        if B in self.graphs:
-            return self.graphs[B]
+    def _decode_graph(self, B, with_processors=False):
+        """Decode graph of batch bucket B, keyed (B, with_processors). The plain entry is what every step of
+        requests without logit processors replays; the processor variant (captured lazily, like any bucket)
+        adds the processor kernel between lm_head and the top-k and appends its per-row argument block to the
+        packed buffer."""
+        key = (B, bool(with_processors))
+        if key in self.graphs:
+            return self.graphs[key]
         from ..ops.native import decode_partitions
 
         m = self.model
@@ -642,7 +783,9 @@ class LLMEngine:
         mb = self.max_blocks
         meta_n = 4 * B + B * mb + (4 * B + B * mb) % 2  # even: the sampling block holds int64 seeds
         # ONE H2D copy per step: [decode metadata | sampling params (6B) | carry map (B)]
-        packed = torch.zeros(meta_n + 7 * B, dtype=torch.int32, device=dev)
+        # (+ with processors: [history rows | penalty | n-gram size | ban count | ban ids (B x BAN_IDS_MAX)])
+        packed = torch.zeros(meta_n + 7 * B + ((4 + BAN_IDS_MAX) * B if with_processors else 0), dtype=torch.int32,
+                             device=dev)
         ids, pos, slots, kvl = (packed[i * B:(i + 1) * B] for i in range(4))
         carry = packed[meta_n + 6 * B:meta_n + 7 * B]
         bt = packed[4 * B:4 * B + B * mb].view(B, mb)
@@ -655,15 +798,24 @@ class LLMEngine:
         out_tok = self._tok_out[:B]
         inp = StepInput(ids, pos, slots, meta, None, carry=carry, carry_src=self._tok_out)
 
+        proc = None
+        if with_processors:
+            # the kernel stores ids[b] (already resolved by the embedding kernel for carried rows) at
+            # hist[row][pos[b]] before it reads the row's history
+            proc = self._proc_views(packed[meta_n + 7 * B:], B)
+            proc["ids"], proc["pos"] = ids, pos
+
         def run():
             logits = m.forward(inp)
             self._sample_rows(logits, samp["temps"], samp["ks"], samp["ps"], samp["seeds"], samp["steps"],
-                              out=out_tok)
+                              out=out_tok, proc=proc)
 
-        entry = dict(packed=packed, samp=samp, out=out_tok, run=run, graph=None, meta=meta, inp=inp)
+        entry = dict(packed=packed, samp=samp, out=out_tok, run=run, graph=None, meta=meta, inp=inp, proc=proc)
         if self.use_graphs:
             kvl.fill_(1)  # scratch-only rows while capturing
             carry.fill_(-1)
+            if proc is not None:
+                proc["rows"].fill_(-1)  # no history row is touched while capturing
             # the eager warm-up runs below sample into the shared _tok_out, which may hold the in-flight
             # step's tokens that the next step carries (a graph captured lazily mid-pipeline): restore it
             saved = self._tok_out.clone()
@@ -680,7 +832,7 @@ class LLMEngine:
                 run()
             self._tok_out.copy_(saved)
             entry["graph"] = g
-        self.graphs[B] = entry
+        self.graphs[key] = entry
         return entry
 
     def warmup_graphs(self, sizes=None):
@@ -734,7 +886,8 @@ class LLMEngine:
         n = len(seqs)
         carried = [id(s) in prev_row for s in seqs]
         B = self._bucket(n)
-        e = self._decode_graph(B)
+        with_proc = any(s.hist_row >= 0 for s in seqs)
+        e = self._decode_graph(B, with_proc)
         samp = self._sampling_host(seqs, pad_to=B)
         steps = samp[5 * B:5 * B + n]
         steps += np.asarray(carried, dtype=np.int32)  # sampling step index of the token being produced
@@ -742,7 +895,13 @@ class LLMEngine:
         # _tok_out, row = that step's row) inside the graph's embedding kernel: no extra copy / gather
         carry = np.full(B, -1, dtype=np.int32)
         carry[:n] = [prev_row[id(s)] if c else -1 for s, c in zip(seqs, carried)]
-        host = np.concatenate([self._decode_inputs_async(seqs, B, carried), samp, carry])
+        parts = [self._decode_inputs_async(seqs, B, carried), samp, carry]
+        if with_proc:
+            # tokens generated before the one this step samples: a carried row's in-flight token counts, as
+            # in `steps` above
+            parts.append(self._proc_host(seqs, [len(s.out) + int(c) for s, c in zip(seqs, carried)], pad_to=B))
+            self.stats["logit_proc_steps"] += 1
+        host = np.concatenate(parts)
         e["packed"].copy_(self._h2d_i32(host), non_blocking=True)
         forced = self._engine_fault_hook()
         if self._timing is not None:
@@ -785,9 +944,7 @@ class LLMEngine:
         if step is None:
             return []
         step["event"].synchronize()
-        for sid in self._free_after:  # rows of the step before `step`: done with those blocks now
-            self.bm.free(sid)
-        self._free_after = []
+        self._free_deferred()  # rows of the step before `step`: done with those blocks now
         if self._kernel_fault():
             return None  # the caller discards this step (and the one in flight behind it)
         tok = step["host_out"][:step["n"]].tolist()
@@ -838,9 +995,7 @@ class LLMEngine:
             native.MLP_ENGINE = False
         self.graphs.clear()
         self._inflight = None
-        for sid in self._free_after:
-            self.bm.free(sid)
-        self._free_after = []
+        self._free_deferred()
         n = 0
         for step in steps:
             if step is None:
@@ -864,9 +1019,7 @@ class LLMEngine:
             self._recover_engine_fault([step])
             self.stats["decode_s"] += time.perf_counter() - t0
             return []
-        for sid in self._free_after:
-            self.bm.free(sid)
-        self._free_after = []
+        self._free_deferred()
         self.stats["decode_s"] += time.perf_counter() - t0
         return fin
 
@@ -876,14 +1029,23 @@ class LLMEngine:
         finished = []
         if not seqs:
             return finished
+        gen = [len(s.out) for s in seqs]
+        with_proc = any(s.hist_row >= 0 for s in seqs)
+        if with_proc:
+            self.stats["logit_proc_steps"] += 1
         if self.is_cuda:
             B = self._bucket(n)
-            e = self._decode_graph(B)
-            host = np.concatenate([self._decode_inputs_host(seqs, B), self._sampling_host(seqs, pad_to=B),
-                                   np.full(B, -1, dtype=np.int32)])
-            e["packed"].copy_(self._h2d_i32(host), non_blocking=True)
+            e = self._decode_graph(B, with_proc)
+            parts = [self._decode_inputs_host(seqs, B), self._sampling_host(seqs, pad_to=B),
+                     np.full(B, -1, dtype=np.int32)]
+            if with_proc:
+                parts.append(self._proc_host(seqs, gen, pad_to=B))
+            e["packed"].copy_(self._h2d_i32(np.concatenate(parts)), non_blocking=True)
             if full_vocab:  # eager forward, exact sampler over the whole vocabulary
-                tok = self._sample_full_vocab(self.model.forward(e["inp"])[:n], seqs)
+                proc = None
+                if with_proc:
+                    proc = {k: (v[:n] if v is not None else None) for k, v in e["proc"].items()}
+                tok = self._sample_full_vocab(self.model.forward(e["inp"])[:n], seqs, proc=proc)
             else:
                 forced = self._engine_fault_hook()
                 if e["graph"] is not None:
@@ -905,10 +1067,11 @@ class LLMEngine:
             meta = AttnMeta("decode", kvl, t[4 * n:4 * n + n * mb].view(n, mb), host_kv_lens=kvl.tolist())
             inp = StepInput(t[:n], t[n:2 * n], t[2 * n:3 * n], meta, None)
             logits = self.model.forward(inp)
+            proc = self._proc_tensors(seqs, t[n:2 * n], gen, ids=t[:n]) if with_proc else None
             if full_vocab:
-                tok = self._sample_full_vocab(logits, seqs)
+                tok = self._sample_full_vocab(logits, seqs, proc=proc)
             else:
-                tok = self._sample_rows(logits, *self._sampling_tensors(seqs)).tolist()
+                tok = self._sample_rows(logits, *self._sampling_tensors(seqs), proc=proc).tolist()
             if self._kernel_fault():
                 self._recover_engine_fault([dict(seqs=seqs)])
                 self.stats["decode_s"] += time.perf_counter() - t0

@@ -85,6 +85,10 @@ _SIGS = {
     "ragk_topk_candidates": [P, I, I, I, I, I, I, P, P, S],
     "ragk_sample_candidates": [P, P, I, I, P, P, P, P, P, P, P, S],
     "ragk_sample_candidates_lists": [P, P, I, I, I, P, P, P, P, P, P, P, S],
+    # csrc/kernels/logits_proc.hip (history-dependent logit processors)
+    "ragk_logits_proc_max_hist": [],
+    "ragk_hist_write": [P, P, P, P, I, I, I, S],
+    "ragk_logits_process": [P, I, I, I, I, P, P, P, P, I, I, P, P, P, I, P, S],
     "ragk_l2_scan_groups": [I, I, I],
     "ragk_l2_search_groups": [I, I, I, I, I],
     "ragk_l2_search_set_mfma_min_nq": [I],

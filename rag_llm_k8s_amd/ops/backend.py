@@ -255,6 +255,13 @@ class TorchBackend:
             i = torch.cat([i, torch.full((i.shape[0], K - k), -1)], 1)
         return v, (i + vocab_offset).int()
 
+    # history-dependent logit processors (repetition penalty, n-gram ban, min_new_tokens) -------------
+    def hist_write(self, ids, rows, pos, hist):
+        return R.hist_write(ids, rows, pos, hist)
+
+    def logits_process(self, logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, ban_ids, ban_count):
+        return R.logits_process(logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, ban_ids, ban_count)
+
     def sample_candidates(self, cand_v, cand_i, temps, top_ks, top_ps, seeds, steps, list_len=None):
         out = torch.empty(cand_v.shape[0], dtype=torch.int32)
         for b in range(cand_v.shape[0]):
@@ -416,6 +423,12 @@ class NativeBackend(TorchBackend):
 
     def topk_candidates(self, logits, K, vocab_offset=0, max_cand=512, chunks=None):
         return self.n.topk_candidates(logits, K, vocab_offset=vocab_offset, max_cand=max_cand, chunks=chunks)
+
+    def hist_write(self, ids, rows, pos, hist):
+        return self.n.hist_write(ids, rows, pos, hist)
+
+    def logits_process(self, logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, ban_ids, ban_count):
+        return self.n.logits_process(logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, ban_ids, ban_count)
 
     def sample_candidates(self, cand_v, cand_i, temps, top_ks, top_ps, seeds, steps, list_len=None):
         return self.n.sample_candidates(cand_v, cand_i, temps, top_ks, top_ps, seeds, steps, list_len=list_len)

@@ -1408,6 +1408,64 @@ def sample_candidates(cand_v, cand_i, temps, top_ks, top_ps, seeds, steps, out_t
     return out_tok
 
 
+# ----------------------------------------------------------------------------- logit processors
+def logits_proc_max_hist():
+    """Longest token-history row (hist.shape[1]) the processor kernel stages in LDS."""
+    return int(_lib.lib().ragk_logits_proc_max_hist())
+
+
+def _i32_vec(t, n, dev, name):
+    _req(t.dtype == torch.int32 and t.is_cuda and t.device == dev and t.dim() == 1 and t.numel() == n
+         and t.is_contiguous(), "%s must be a contiguous int32 [%d] tensor on the launch device" % (name, n))
+
+
+def _hist_buf(hist, dev):
+    _req(hist.dtype == torch.int32 and hist.is_cuda and hist.device == dev and hist.dim() == 2
+         and hist.is_contiguous() and hist.shape[0] >= 1 and hist.shape[1] >= 1,
+         "hist must be a contiguous int32 [rows, max_len] tensor on the launch device")
+
+
+def hist_write(ids, rows, pos, hist):
+    """Prefill scatter of the token history: hist[rows[i], pos[i]] = ids[i]; rows < 0 are skipped (and, as a
+    bound, rows / positions outside the buffer)."""
+    _hist_buf(hist, hist.device)
+    T = ids.numel()
+    for t, name in ((ids, "ids"), (rows, "rows"), (pos, "pos")):
+        _i32_vec(t, T, hist.device, name)
+    check(_lib.lib().ragk_hist_write(ids.data_ptr(), rows.data_ptr(), pos.data_ptr(), hist.data_ptr(), hist.shape[0],
+                                     hist.shape[1], T, stream_ptr()), "ragk_hist_write")
+    return hist
+
+
+def logits_process(logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, ban_ids, ban_count):
+    """Repetition penalty, n-gram ban and min_new_tokens ban list, in place on fp32 logits [B, V] (a vocab shard
+    starting at vocab_offset). One workgroup per row; row b reads hist[rows[b], :pos[b] + 1] (rows[b] < 0: the
+    row is not touched). With `ids` (decode) hist[rows[b], pos[b]] = ids[b] is stored first. The kernel stages
+    a whole history row in LDS: a hist wider than logits_proc_max_hist() is refused here."""
+    _req(logits.dtype == torch.float32 and logits.is_cuda and logits.dim() == 2 and logits.stride(1) == 1, "logits fp32")
+    B, V = logits.shape
+    dev = logits.device
+    _req(V >= 1 and (B <= 1 or logits.stride(0) >= V), "logits rows must not overlap")
+    _hist_buf(hist, dev)
+    _req(hist.shape[1] <= logits_proc_max_hist(),
+         "history rows of %d entries exceed the %d the kernel stages" % (hist.shape[1], logits_proc_max_hist()))
+    for t, name in ((rows, "rows"), (pos, "pos"), (ngram, "ngram"), (ban_count, "ban_count")):
+        _i32_vec(t, B, dev, name)
+    if ids is not None:
+        _i32_vec(ids, B, dev, "ids")
+    _req(penalty.dtype == torch.float32 and penalty.is_cuda and penalty.device == dev and penalty.dim() == 1
+         and penalty.numel() == B and penalty.is_contiguous(), "penalty must be a contiguous fp32 [B] tensor")
+    _req(ban_ids.dtype == torch.int32 and ban_ids.is_cuda and ban_ids.device == dev and ban_ids.dim() == 2
+         and ban_ids.shape[0] == B and ban_ids.shape[1] >= 1 and ban_ids.is_contiguous(),
+         "ban_ids must be a contiguous int32 [B, width] tensor")
+    check(_lib.lib().ragk_logits_process(logits.data_ptr(), logits.stride(0) if B > 1 else max(V, logits.stride(0)),
+                                         B, V, int(vocab_offset), ptr(ids), rows.data_ptr(), pos.data_ptr(),
+                                         hist.data_ptr(), hist.shape[0], hist.shape[1], penalty.data_ptr(),
+                                         ngram.data_ptr(), ban_ids.data_ptr(), ban_ids.shape[1],
+                                         ban_count.data_ptr(), stream_ptr()), "ragk_logits_process")
+    return logits
+
+
 # ----------------------------------------------------------------------------- search
 def l2_search_set_mfma_min_nq(n):
     """Batches of at least n queries (k <= 8, d % 32 == 0) take the MFMA ||x||^2+||q||^2-2x.q path."""

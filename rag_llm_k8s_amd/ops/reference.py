@@ -244,6 +244,65 @@ def sample_from_logits_candidates(vals, idx, temperature, top_p, u):
     return ki, p, int(ki[min(j, len(ki) - 1)])
 
 
+LOGITS_PROC_MAX_HIST = 32768  # history entries per row the native kernel stages (csrc/kernels/logits_proc.hip)
+LOGITS_PROC_MAX_NGRAM = 8
+
+
+def hist_write(ids, rows, pos, hist):
+    """Token-history scatter: hist[rows[i], pos[i]] = ids[i] for every i with rows[i] >= 0 (in place)."""
+    keep = rows >= 0
+    hist[rows[keep].long(), pos[keep].long()] = ids[keep].to(hist.dtype)
+    return hist
+
+
+def repetition_penalty_row(x, seq, penalty, vocab_offset=0):
+    """transformers' RepetitionPenaltyLogitsProcessor on one (shard of a) row, in place: every distinct id of
+    `seq` inside [vocab_offset, vocab_offset + len(x)) gets x * p if x < 0 else x / p, once."""
+    t = torch.unique(seq.long()) - vocab_offset
+    t = t[(t >= 0) & (t < x.numel())]
+    v = x[t]
+    x[t] = torch.where(v < 0, v * penalty, v / penalty)
+    return x
+
+
+def ngram_banned(seq, n):
+    """transformers' NoRepeatNGramLogitsProcessor: the ids t[j+n-1] of every j in [0, L-n] whose n-1 tokens
+    t[j..j+n-2] equal the last n-1 tokens of the sequence (nothing while L + 1 < n)."""
+    L = seq.numel()
+    if n < 1 or L < n:
+        return seq[:0].long()
+    if n == 1:
+        return seq.long()
+    win = seq.unfold(0, n, 1)  # [L-n+1, n]
+    hit = (win[:, :n - 1] == seq[L - n + 1:]).all(1)
+    return win[hit, n - 1].long()
+
+
+def logits_process(logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, ban_ids, ban_count):
+    """History-dependent logit processors on fp32 logits [B, V] (a vocab shard starting at vocab_offset), in
+    place, in transformers' order: repetition penalty, then the -inf writes of the n-gram ban and of the
+    min_new_tokens ban list (ban_ids[b, :ban_count[b]]). Row b reads history row rows[b] (< 0: the row is left
+    untouched) of length pos[b] + 1; with `ids` given (decode) hist[rows[b], pos[b]] = ids[b] is stored first."""
+    B, V = logits.shape
+    for b in range(B):
+        r = int(rows[b])
+        if r < 0:
+            continue
+        p = int(pos[b])
+        if ids is not None:
+            hist[r, p] = ids[b]
+        seq = hist[r, :p + 1]
+        x = logits[b]
+        pen = float(penalty[b])
+        if pen != 1.0:
+            repetition_penalty_row(x, seq, torch.tensor(pen, dtype=torch.float32), vocab_offset)
+        n = int(ngram[b])
+        bans = [ngram_banned(seq, n) if n > 0 else seq[:0].long(), ban_ids[b, :int(ban_count[b])].long()]
+        t = torch.cat(bans) - vocab_offset
+        x[t[(t >= 0) & (t < V)]] = float("-inf")
+    return logits
+
+
 def l2_knn(xb, q, k):
     """faiss IndexFlatL2.search: squared L2, ascending; pad (-1, FLT_MAX)."""
     n = xb.shape[0]

@@ -13,6 +13,9 @@ New (documents can be listed, removed, replaced and filtered on; the reference c
   POST /generate     optional "filenames": [str, ...] -> the context comes from these documents only
   POST /generate     optional "rerank": false -> skip the cross-encoder stage for this query (RERANK_MODEL set);
                      "rerank": true without RERANK_MODEL -> 500 {"error"} naming it
+  POST /generate     optional "repetition_penalty": float > 0, "no_repeat_ngram_size": 0..8, "min_new_tokens":
+                     0..MAX_NEW_TOKENS -> override REPETITION_PENALTY / NO_REPEAT_NGRAM_SIZE / MIN_NEW_TOKENS for
+                     this request (transformers' generate() semantics); a refused value -> 400 {"error"}
   POST /upload_pdf?replace=1 (or form field replace=1) -> the document's old chunks are replaced
   GET  /documents    -> {"documents": [{"filename", "chunks"}]}
   DELETE /documents/<filename> -> 200 {"message", "chunks_removed"} | 404 {"error"}
@@ -41,6 +44,14 @@ def create_app(service) -> Flask:
             kw = {"filenames": filenames} if filenames else {}
             if data.get("rerank") is not None:  # per-request switch of the cross-encoder stage
                 kw["rerank"] = bool(data["rerank"])
+            # per-request logit processors: the service's default SamplingParams with these fields replaced
+            over = {k: data[k] for k in service.REQUEST_PARAM_FIELDS if data.get(k) is not None}
+            if over:
+                try:
+                    kw["params"] = service.request_params(over)
+                except ValueError as e:  # a value the engine refuses
+                    metrics.inc("requests", route="generate", status="400")
+                    return jsonify({"error": str(e)}), 400
             out = service.generate(user_prompt, debug=debug, **kw)
             metrics.inc("requests", route="generate", status="200")
             return jsonify(out)

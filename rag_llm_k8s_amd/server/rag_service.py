@@ -13,6 +13,7 @@ packed batches instead of one chunk at a time.
 """
 from __future__ import annotations
 
+import dataclasses
 import faulthandler
 import logging
 import os
@@ -279,7 +280,11 @@ class RagService:
         stop = tuple(eos) if isinstance(eos, list) else ((eos,) if eos is not None else ())
         self.params = SamplingParams(max_new_tokens=cfg.max_new_tokens, temperature=cfg.temperature,
                                      top_p=cfg.top_p, top_k=cfg.top_k, do_sample=do_sample, stop_token_ids=stop,
-                                     ignore_eos=bool(getattr(cfg, "ignore_eos", False)))
+                                     ignore_eos=bool(getattr(cfg, "ignore_eos", False)),
+                                     repetition_penalty=float(getattr(cfg, "repetition_penalty", 1.0)),
+                                     no_repeat_ngram_size=int(getattr(cfg, "no_repeat_ngram_size", 0)),
+                                     min_new_tokens=int(getattr(cfg, "min_new_tokens", 0)))
+        llm_engine.check_params(self.params)
         self.loop = EngineLoop(llm_engine, control=control)
         # tensor-parallel group (set by the TP server): PDF ingest is data-parallel over it and, with
         # INDEX_SHARDED, every rank holds a row shard of the index (both run as collective jobs)
@@ -419,6 +424,25 @@ class RagService:
                 raise ValueError("prompt of %d tokens exceeds the model limit %d" % (len(ids), limit))
             ids = ids[len(ids) - limit:]  # keep the question and "Chatbot:" suffix
         return ids
+
+    # per-request logit-processor fields of /generate (JSON names = SamplingParams names) and their JSON types
+    REQUEST_PARAM_FIELDS = {"repetition_penalty": (int, float), "no_repeat_ngram_size": (int,),
+                            "min_new_tokens": (int,)}
+
+    def request_params(self, overrides):
+        """The service's default SamplingParams with a request's logit-processor fields replaced. Raises
+        ValueError (the route's 400) for a field of the wrong JSON type or a value the engine refuses."""
+        kw = {}
+        for k, v in overrides.items():
+            types = self.REQUEST_PARAM_FIELDS.get(k)
+            if types is None:
+                raise ValueError("unknown sampling field %r" % (k,))
+            if isinstance(v, bool) or not isinstance(v, types):
+                raise ValueError("%s must be %s (got %r)" % (k, "a number" if float in types else "an integer", v))
+            kw[k] = float(v) if float in types else v
+        p = dataclasses.replace(self.params, **kw)
+        self.engine.check_params(p)
+        return p
 
     def generate(self, user_prompt, params=None, debug=False, filenames=None, rerank=None):
         """Synchronous /generate (thread-safe). filenames: only these documents supply the context.

@@ -21,7 +21,7 @@ def replay_probe(eng, B, mid):
     """Back-to-back replays of the B-bucket graph from the engine's current (mid-run) metadata: the GPU time
     of one decode step with no host work in between; DA_REPLAY_MODES=h2d,d2h,both,adv,sync,pipe,pipe_copy add
     the engine's per-step copies / waits around the replays."""
-    e = eng.graphs.get(B)
+    e = eng.graphs.get((B, False))
     if e is None or e["graph"] is None:
         return
     pk = e["packed"]

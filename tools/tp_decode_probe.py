@@ -77,7 +77,7 @@ def main():
         for _ in range(max(1, steps // 2)):
             eng.step()
         torch.cuda.synchronize()
-        e = eng.graphs.get(B)
+        e = eng.graphs.get((B, False))
         live = int((e["packed"][3 * B:4 * B] > 1).sum())
         e["graph"].replay()
         torch.cuda.synchronize()
