@@ -47,6 +47,9 @@ class RagConfig:
     repetition_penalty: float = 1.0
     no_repeat_ngram_size: int = 0
     min_new_tokens: int = 0
+    # per-token log-probabilities with this many alternatives (0..20) in every response; None (unset) = off.
+    # A /generate request may set "logprobs" itself.
+    logprobs: Optional[int] = None
     do_sample: Optional[bool] = None  # None -> generation_config.json (reference: model.generate defaults)
     seed: int = 0
     tp_size: int = 1
@@ -95,7 +98,7 @@ class RagConfig:
             "CHUNK_OVERLAP": ("chunk_overlap", int), "MAX_NEW_TOKENS": ("max_new_tokens", int),
             "TEMPERATURE": ("temperature", float), "TOP_P": ("top_p", float), "TOP_K": ("top_k", int),
             "REPETITION_PENALTY": ("repetition_penalty", float), "NO_REPEAT_NGRAM_SIZE": ("no_repeat_ngram_size", int),
-            "MIN_NEW_TOKENS": ("min_new_tokens", int),
+            "MIN_NEW_TOKENS": ("min_new_tokens", int), "LOGPROBS": ("logprobs", int),
             "SEED": ("seed", int), "TP_SIZE": ("tp_size", int), "DTYPE": ("dtype", str), "DEVICE": ("device", str),
             "INDEX_TYPE": ("index_type", str), "IVF_NLIST": ("ivf_nlist", int), "IVF_NPROBE": ("ivf_nprobe", int),
             "REINGEST_APPEND": ("reingest_append", bool), "MAX_BATCH": ("max_batch", int),

@@ -35,6 +35,8 @@ import torch
 from ..models.llama import StepInput
 from ..ops.backend import AttnMeta
 from ..ops.fp8 import kv_cache_dtype_name, kv_cache_torch_dtype
+# per-token log-probabilities (csrc/kernels/logprobs.hip): LOGPROBS_MAX = most alternatives per position
+from ..ops.reference import LOGPROBS_MAX, lse_chunks
 from ..utils import faults
 from .kv_manager import BLOCK, make_block_manager
 
@@ -68,6 +70,10 @@ class SamplingParams:
     repetition_penalty: float = 1.0  # RepetitionPenaltyLogitsProcessor
     no_repeat_ngram_size: int = 0  # NoRepeatNGramLogitsProcessor, 0..NGRAM_MAX
     min_new_tokens: int = 0  # MinNewTokensLengthLogitsProcessor over eos + stop_token_ids
+    # None = off; N in 0..LOGPROBS_MAX: every generated token's log-probability plus the N most likely
+    # alternatives, log_softmax of the fp32 logits after the processors above and before temperature / top-k /
+    # top-p (transformers' `scores` of a greedy generate; the unwarped model distribution for sampled requests)
+    logprobs: Optional[int] = None
 
     def uses_processors(self) -> bool:
         return (self.repetition_penalty != 1.0 or self.no_repeat_ngram_size > 0
@@ -100,6 +106,11 @@ class Sequence:
         self.done = threading.Event()
         self.user = None  # opaque payload for the caller
         self.hist_row = -1  # row of the engine's device token history (-1: no logit processors)
+        # per generated token (len == len(out) at all times) for a request with params.logprobs, else None:
+        # its log-probability, and the top-N alternatives as [(id, logprob)] by (logprob desc, id asc)
+        want = getattr(params, "logprobs", None) is not None
+        self.logprobs: Optional[List[float]] = [] if want else None
+        self.top_logprobs: Optional[List[list]] = [] if want else None
 
     @property
     def length(self):
@@ -193,6 +204,10 @@ class LLMEngine:
         self._hist_free = None
         self._hist_after = []
         self.stats["logit_proc_steps"] = 0
+        # per-token log-probabilities: steps that had a row asking for them, and the two pinned read-back
+        # buffers of the asynchronous pipeline (allocated at the first such step, alternated like _out_pins)
+        self.stats["logprob_steps"] = 0
+        self._lp_pins = None
 
     # ------------------------------------------------------------------ requests
     def add_request(self, prompt_ids, params: SamplingParams, seed: Optional[int] = None) -> Sequence:
@@ -232,6 +247,13 @@ class LLMEngine:
                              % (p.max_new_tokens, m))
         if m > 0 and not p.ignore_eos and len(self._stop_ids(p)) > BAN_IDS_MAX:
             raise ValueError("min_new_tokens: at most %d eos + stop ids" % BAN_IDS_MAX)
+        lp = p.logprobs
+        if lp is not None:
+            if isinstance(lp, bool) or not isinstance(lp, int) or not 0 <= lp <= LOGPROBS_MAX:
+                raise ValueError("logprobs must be None or an integer in 0..%d (got %r)" % (LOGPROBS_MAX, lp))
+            if LOGPROBS_MAX > self.K:
+                raise ValueError("logprobs: the engine's candidate lists (top_k_cap = %d) are shorter than %d"
+                                 % (self.K, LOGPROBS_MAX))
         if p.uses_processors() and self.is_cuda:
             from ..ops.native import logits_proc_max_hist
             if self.max_model_len > logits_proc_max_hist():
@@ -297,6 +319,55 @@ class LLMEngine:
         be = self.model.be
         be.logits_process(lg, self.model.w.vocab_offset, proc["ids"], proc["rows"], proc["pos"], self._hist,
                           proc["penalty"], proc["ngram"], proc["ban_ids"], proc["ban_count"])
+
+    # ------------------------------------------------------------------ per-token log-probabilities
+    LP_WORDS = 2 + 2 * LOGPROBS_MAX  # output words per row: lse | token logprob | top logprobs | top ids
+
+    def _lp_host(self, seqs, pad_to=None):
+        """int32 [n]: alternatives per row, -1 for plain and padded rows."""
+        nlp = np.full(pad_to or len(seqs), -1, dtype=np.int32)
+        for i, s in enumerate(seqs):
+            if s.logprobs is not None:
+                nlp[i] = s.params.logprobs
+        return nlp
+
+    @staticmethod
+    def _lp_views(buf, n):
+        """(lse [n], token logprob [n], top logprobs [n, LOGPROBS_MAX], top ids [n, LOGPROBS_MAX]) views of an
+        int32 [LP_WORDS * n] buffer: one allocation, so one copy brings a step's values to the host."""
+        L = LOGPROBS_MAX
+        return (buf[0:n].view(torch.float32), buf[n:2 * n].view(torch.float32),
+                buf[2 * n:(2 + L) * n].view(torch.float32).view(n, L), buf[(2 + L) * n:(2 + 2 * L) * n].view(n, L))
+
+    def _lp_block(self, seqs):
+        """Logprob argument block of an eager sampling call (None if no row asks): nlp on the device and a
+        fresh output buffer."""
+        if not any(s.logprobs is not None for s in seqs):
+            return None
+        self.stats["logprob_steps"] += 1
+        n = len(seqs)
+        return dict(nlp=self._h2d_i32(self._lp_host(seqs)), n=n,
+                    buf=torch.zeros(self.LP_WORDS * n, dtype=torch.int32, device=self.device))
+
+    def _lp_values(self, host, n, seqs):
+        """Per sequence None or (token logprob, [(id, logprob)] of its N alternatives) from a host copy of an
+        output buffer laid out for n rows (_lp_views)."""
+        _, tl, tp, ti = self._lp_views(host, n)
+        tl, tp, ti = tl.numpy(), tp.numpy(), ti.numpy()
+        out = []
+        for i, s in enumerate(seqs):
+            if s.logprobs is None:
+                out.append(None)
+                continue
+            k = s.params.logprobs
+            out.append((float(tl[i]), [(int(ti[i, j]), float(tp[i, j])) for j in range(k)]))
+        return out
+
+    def _lp_pin(self, idx, words):
+        if self._lp_pins is None:
+            cap = self.LP_WORDS * max(self.buckets + [self.max_batch, 1])
+            self._lp_pins = [torch.empty(cap, dtype=torch.int32, pin_memory=self.is_cuda) for _ in range(2)]
+        return self._lp_pins[idx][:words]
 
     def add_sequence(self, s: Sequence):
         with self.lock:
@@ -467,10 +538,14 @@ class LLMEngine:
         self.running.remove(s)
         s.done.set()
 
-    def _accept(self, s, tok):
+    def _accept(self, s, tok, lp=None):
+        """lp: (token logprob, alternatives) of a request with logprobs, accepted with (and only with) its token."""
         if s.t_first is None:
             s.t_first = time.perf_counter()
         s.out.append(int(tok))
+        if s.logprobs is not None:
+            s.logprobs.append(lp[0])
+            s.top_logprobs.append(lp[1])
         p = s.params
         if not p.ignore_eos and (int(tok) in self.eos or int(tok) in p.stop_token_ids):
             return "stop"
@@ -519,12 +594,13 @@ class LLMEngine:
             self._warned_topk = True
         return bad
 
-    def _sample_full_vocab(self, logits, seqs, proc=None):
+    def _sample_full_vocab(self, logits, seqs, proc=None, want_lp=False):
         """Exact temperature -> top-k (if 0 < top_k) -> top-p -> multinomial over the whole vocabulary
         (transformers' LogitsProcessor order, [dep] generation/utils.py:1311-1322). Under TP the vocab
         shards are all-gathered first. Uniforms come from torch.Generator(seed * 1000003 + step), as in
         the torch backend's sampler. `proc`: the logit processors' argument block (_proc_tensors), applied
-        first, on this rank's shard."""
+        first, on this rank's shard. want_lp: also return the per-sequence logprob values (_lp_values' form)
+        of the rows that ask, computed from the gathered fp32 row with the reference functions."""
         w = self.model.w
         if proc is not None:
             self._apply_processors(logits[:, :w.vocab_valid] if w.vocab_valid < logits.shape[1] else logits, proc)
@@ -568,11 +644,31 @@ class LLMEngine:
             u = float(torch.rand(1, generator=g)) * float(c[-1])
             j = min(int(torch.searchsorted(c, torch.tensor([u]), right=True)[0]), int(keep.sum()) - 1)
             toks.append(int(order[j]))
-        return toks
+        if not want_lp:
+            return toks
+        from ..ops import reference as R
 
-    def _sample_rows(self, logits, temps, ks, ps, seeds, steps, out=None, proc=None):
+        vals = []
+        for b, s in enumerate(seqs):
+            if s.logprobs is None:
+                vals.append(None)
+                continue
+            x = lg[b:b + 1]
+            V = x.shape[1]
+            sv, order = torch.sort(x, descending=True, stable=True)  # one list: the whole row, (value desc, id asc)
+            _, tl, tp, ti = R.logprobs_finish(R.lse_partials(x, lse_chunks(V, 1)), sv, order.int(), V,
+                                              torch.tensor([toks[b]], dtype=torch.int32),
+                                              torch.tensor([s.params.logprobs], dtype=torch.int32))
+            k = s.params.logprobs
+            vals.append((float(tl[0]), [(int(ti[0, j]), float(tp[0, j])) for j in range(k)]))
+        return toks, vals
+
+    def _sample_rows(self, logits, temps, ks, ps, seeds, steps, out=None, proc=None, lp=None):
         """`proc` (optional): the logit processors' argument block; their kernel then runs in place on the
-        logits before the candidate top-k (temperature / top-k / top-p follow, as in transformers)."""
+        logits before the candidate top-k (temperature / top-k / top-p follow, as in transformers).
+        `lp` (optional): the logprob block (nlp [B] on the device, buf = the output words of _lp_views): two
+        more launches, lse_partials next to the top-k on the same logits view and logprobs_finish after the
+        sampler, on the candidates it sampled from."""
         be = self.model.be
         w = self.model.w
         lg = logits[:, :w.vocab_valid] if w.vocab_valid < logits.shape[1] else logits
@@ -588,9 +684,22 @@ class LLMEngine:
             chunks = max(1, min(logits.shape[1] // SMALL_BATCH_TOPK_CHUNK, (2048 // self.tp_size) // self.K, 64))
         cv, ci = be.topk_candidates(lg.contiguous() if not lg.is_contiguous() else lg, self.K,
                                     vocab_offset=w.vocab_offset, chunks=chunks)
+        part = None
+        if lp is not None:
+            # chunk count from the padded shard width: every TP rank contributes the same number of partials.
+            # Like the top-k's above it also goes with the rows of this call (the bucket inside a graph, n on the
+            # eager path): the default buckets hold 64, so both paths land on the same side of the batch-64
+            # threshold and the lse bits agree; a custom `graph_buckets` that serves n <= 64 from a larger
+            # bucket chunks the two paths differently, and their lse then agree to rounding only.
+            part = be.lse_partials(lg, lse_chunks(logits.shape[1], logits.shape[0]))
         if self.tp_size > 1:
             cv, ci = self._gather_candidates(cv, ci)
+            if part is not None:
+                part = self._gather_partials(part)
         tok = be.sample_candidates(cv, ci, temps, ks, ps, seeds, steps, list_len=self.K)
+        if lp is not None:
+            o_lse, o_tl, o_tp, o_ti = self._lp_views(lp["buf"], lp["n"])
+            be.logprobs_finish(part, cv, ci, self.K, tok, lp["nlp"], o_lse, o_tl, o_tp, o_ti)
         if out is not None:
             out.copy_(tok)
             return out
@@ -615,6 +724,22 @@ class LLMEngine:
             gv, gi = torch.stack(lv), torch.stack(li)
         return gv.permute(1, 0, 2).reshape(B, self.tp_size * K).contiguous(), \
             gi.permute(1, 0, 2).reshape(B, self.tp_size * K).contiguous()
+
+    def _gather_partials(self, part):
+        """lse partials [B, C, 2] of every TP rank -> [B, tp * C, 2], rank-major (identical on every rank)."""
+        if self.comm is not None:
+            return self.comm.gather_partials(part)
+        import torch.distributed as dist
+
+        B, C, _ = part.shape
+        if part.is_cuda:
+            g = torch.empty((self.tp_size, B, C, 2), dtype=part.dtype, device=part.device)
+            dist.all_gather_into_tensor(g, part.contiguous(), group=self.tp_group)
+        else:  # gloo (CPU plumbing / tests)
+            lp = [torch.empty_like(part) for _ in range(self.tp_size)]
+            dist.all_gather(lp, part.contiguous(), group=self.tp_group)
+            g = torch.stack(lp)
+        return g.permute(1, 0, 2, 3).reshape(B, self.tp_size * C, 2).contiguous()
 
     # ------------------------------------------------------------------ prefill
     def _prefill_input(self, chunks):
@@ -709,18 +834,28 @@ class LLMEngine:
             if out_seqs else None
         if proc is not None:
             self.stats["logit_proc_steps"] += 1
+        # the first generated token's logprobs: the same two launches on this eager sampling call
+        vals = None
         if out_seqs and self._needs_full_vocab(out_seqs):
-            tok = self._sample_full_vocab(logits, out_seqs, proc=proc)
+            # the host computes the values there: no device block, only the step is counted
+            if any(s.logprobs is not None for s in out_seqs):
+                self.stats["logprob_steps"] += 1
+                tok, vals = self._sample_full_vocab(logits, out_seqs, proc=proc, want_lp=True)
+            else:
+                tok = self._sample_full_vocab(logits, out_seqs, proc=proc)
         elif out_seqs:
-            tok = self._sample_rows(logits, *self._sampling_tensors(out_seqs), proc=proc).cpu().tolist()
+            lp = self._lp_block(out_seqs)
+            tok = self._sample_rows(logits, *self._sampling_tensors(out_seqs), proc=proc, lp=lp).cpu().tolist()
+            if lp is not None:
+                vals = self._lp_values(lp["buf"].cpu(), lp["n"], out_seqs)
         else:
             tok = []
             if self.is_cuda:
                 torch.cuda.current_stream(self.device).synchronize()
         for s, start, n in chunks:
             s.computed = start + n
-        for s, t in zip(out_seqs, tok):
-            r = self._accept(s, t)
+        for i, (s, t) in enumerate(zip(out_seqs, tok)):
+            r = self._accept(s, t, vals[i] if vals is not None else None)
             if r:
                 self._finish(s, r)
                 finished.append(s)
@@ -768,12 +903,14 @@ class LLMEngine:
             kvl[:n] = p + 1
         return out
 
-    def _decode_graph(self, B, with_processors=False):
+    def _decode_graph(self, B, with_processors=False, with_logprobs=False):
         """Decode graph of batch bucket B, keyed (B, with_processors). The plain entry is what every step of
         requests without logit processors replays; the processor variant (captured lazily, like any bucket)
         adds the processor kernel between lm_head and the top-k and appends its per-row argument block to the
-        packed buffer."""
-        key = (B, bool(with_processors))
+        packed buffer. A step in which some row wants logprobs replays a further variant keyed
+        (B, with_processors, True): the two logprob launches around the sampler, the rows' alternative counts
+        (nlp) as the last B words of the packed buffer, and entry["lp"]["buf"] as the values' device buffer."""
+        key = (B, bool(with_processors)) + ((True,) if with_logprobs else ())
         if key in self.graphs:
             return self.graphs[key]
         from ..ops.native import decode_partitions
@@ -784,8 +921,9 @@ class LLMEngine:
         meta_n = 4 * B + B * mb + (4 * B + B * mb) % 2  # even: the sampling block holds int64 seeds
         # ONE H2D copy per step: [decode metadata | sampling params (6B) | carry map (B)]
         # (+ with processors: [history rows | penalty | n-gram size | ban count | ban ids (B x BAN_IDS_MAX)])
-        packed = torch.zeros(meta_n + 7 * B + ((4 + BAN_IDS_MAX) * B if with_processors else 0), dtype=torch.int32,
-                             device=dev)
+        # (+ with logprobs: [alternatives per row (B)])
+        proc_n = (4 + BAN_IDS_MAX) * B if with_processors else 0
+        packed = torch.zeros(meta_n + 7 * B + proc_n + (B if with_logprobs else 0), dtype=torch.int32, device=dev)
         ids, pos, slots, kvl = (packed[i * B:(i + 1) * B] for i in range(4))
         carry = packed[meta_n + 6 * B:meta_n + 7 * B]
         bt = packed[4 * B:4 * B + B * mb].view(B, mb)
@@ -802,20 +940,27 @@ class LLMEngine:
         if with_processors:
             # the kernel stores ids[b] (already resolved by the embedding kernel for carried rows) at
             # hist[row][pos[b]] before it reads the row's history
-            proc = self._proc_views(packed[meta_n + 7 * B:], B)
+            proc = self._proc_views(packed[meta_n + 7 * B:meta_n + 7 * B + proc_n], B)
             proc["ids"], proc["pos"] = ids, pos
+        lp = None
+        if with_logprobs:
+            lp = dict(nlp=packed[meta_n + 7 * B + proc_n:meta_n + 7 * B + proc_n + B], n=B,
+                      buf=torch.zeros(self.LP_WORDS * B, dtype=torch.int32, device=dev))
 
         def run():
             logits = m.forward(inp)
             self._sample_rows(logits, samp["temps"], samp["ks"], samp["ps"], samp["seeds"], samp["steps"],
-                              out=out_tok, proc=proc)
+                              out=out_tok, proc=proc, lp=lp)
 
-        entry = dict(packed=packed, samp=samp, out=out_tok, run=run, graph=None, meta=meta, inp=inp, proc=proc)
+        entry = dict(packed=packed, samp=samp, out=out_tok, run=run, graph=None, meta=meta, inp=inp, proc=proc,
+                     lp=lp)
         if self.use_graphs:
             kvl.fill_(1)  # scratch-only rows while capturing
             carry.fill_(-1)
             if proc is not None:
                 proc["rows"].fill_(-1)  # no history row is touched while capturing
+            if lp is not None:
+                lp["nlp"].fill_(-1)  # no logprob output is written while capturing
             # the eager warm-up runs below sample into the shared _tok_out, which may hold the in-flight
             # step's tokens that the next step carries (a graph captured lazily mid-pipeline): restore it
             saved = self._tok_out.clone()
@@ -887,7 +1032,8 @@ class LLMEngine:
         carried = [id(s) in prev_row for s in seqs]
         B = self._bucket(n)
         with_proc = any(s.hist_row >= 0 for s in seqs)
-        e = self._decode_graph(B, with_proc)
+        with_lp = any(s.logprobs is not None for s in seqs)
+        e = self._decode_graph(B, with_proc, with_lp)
         samp = self._sampling_host(seqs, pad_to=B)
         steps = samp[5 * B:5 * B + n]
         steps += np.asarray(carried, dtype=np.int32)  # sampling step index of the token being produced
@@ -901,6 +1047,9 @@ class LLMEngine:
             # in `steps` above
             parts.append(self._proc_host(seqs, [len(s.out) + int(c) for s, c in zip(seqs, carried)], pad_to=B))
             self.stats["logit_proc_steps"] += 1
+        if with_lp:
+            parts.append(self._lp_host(seqs, pad_to=B))
+            self.stats["logprob_steps"] += 1
         host = np.concatenate(parts)
         e["packed"].copy_(self._h2d_i32(host), non_blocking=True)
         forced = self._engine_fault_hook()
@@ -917,11 +1066,15 @@ class LLMEngine:
         self._out_idx ^= 1
         host_out = self._out_pins[self._out_idx]
         host_out[:n].copy_(e["out"][:n], non_blocking=True)
+        lp_host = None
+        if with_lp:  # the step's logprob values ride to the host with its tokens: one more non-blocking copy
+            lp_host = self._lp_pin(self._out_idx, self.LP_WORDS * B)
+            lp_host.copy_(e["lp"]["buf"], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.device))
         for s in seqs:
             s.computed = s.length + (1 if id(s) in prev_row else 0)
-        cur = dict(seqs=seqs, out=e["out"], event=ev, host_out=host_out, n=n)
+        cur = dict(seqs=seqs, out=e["out"], event=ev, host_out=host_out, n=n, lp_host=lp_host, B=B)
         fin = self._collect(prev, in_flight=set(id(s) for s in seqs))
         if fin is None:  # prev failed in-kernel; cur consumed its tokens on the device
             self._recover_engine_fault([prev, cur])
@@ -948,11 +1101,13 @@ class LLMEngine:
         if self._kernel_fault():
             return None  # the caller discards this step (and the one in flight behind it)
         tok = step["host_out"][:step["n"]].tolist()
+        # logprob values are accepted one step late with their token; a discarded row's are dropped with it
+        vals = self._lp_values(step["lp_host"], step["B"], step["seqs"]) if step.get("lp_host") is not None else None
         finished = []
-        for s, t in zip(step["seqs"], tok):
+        for i, (s, t) in enumerate(zip(step["seqs"], tok)):
             if s.status == FINISHED:  # stopped (or aborted) before this step's token was read
                 continue
-            r = self._accept(s, t)
+            r = self._accept(s, t, vals[i] if vals is not None else None)
             self.stats["decode_tokens"] += 1
             if r:
                 self._finish(s, r, defer_free=id(s) in in_flight)
@@ -1033,19 +1188,28 @@ class LLMEngine:
         with_proc = any(s.hist_row >= 0 for s in seqs)
         if with_proc:
             self.stats["logit_proc_steps"] += 1
+        with_lp = any(s.logprobs is not None for s in seqs)
+        vals = None
         if self.is_cuda:
             B = self._bucket(n)
-            e = self._decode_graph(B, with_proc)
+            # a full-vocabulary step computes its logprobs on the host: it needs no graph variant
+            e = self._decode_graph(B, with_proc, with_lp and not full_vocab)
             parts = [self._decode_inputs_host(seqs, B), self._sampling_host(seqs, pad_to=B),
                      np.full(B, -1, dtype=np.int32)]
             if with_proc:
                 parts.append(self._proc_host(seqs, gen, pad_to=B))
+            if with_lp and not full_vocab:
+                parts.append(self._lp_host(seqs, pad_to=B))
+            if with_lp:
+                self.stats["logprob_steps"] += 1
             e["packed"].copy_(self._h2d_i32(np.concatenate(parts)), non_blocking=True)
             if full_vocab:  # eager forward, exact sampler over the whole vocabulary
                 proc = None
                 if with_proc:
                     proc = {k: (v[:n] if v is not None else None) for k, v in e["proc"].items()}
-                tok = self._sample_full_vocab(self.model.forward(e["inp"])[:n], seqs, proc=proc)
+                tok = self._sample_full_vocab(self.model.forward(e["inp"])[:n], seqs, proc=proc, want_lp=with_lp)
+                if with_lp:
+                    tok, vals = tok
             else:
                 forced = self._engine_fault_hook()
                 if e["graph"] is not None:
@@ -1055,6 +1219,8 @@ class LLMEngine:
                 if forced:
                     self._engine_fault_hook(release=True)
                 tok = e["out"][:n].cpu().tolist()
+                if with_lp:
+                    vals = self._lp_values(e["lp"]["buf"].cpu(), B, seqs)
             if self._kernel_fault():  # synchronised by the token read-back above
                 self._recover_engine_fault([dict(seqs=seqs)])
                 self.stats["decode_s"] += time.perf_counter() - t0
@@ -1069,17 +1235,23 @@ class LLMEngine:
             logits = self.model.forward(inp)
             proc = self._proc_tensors(seqs, t[n:2 * n], gen, ids=t[:n]) if with_proc else None
             if full_vocab:
-                tok = self._sample_full_vocab(logits, seqs, proc=proc)
+                tok = self._sample_full_vocab(logits, seqs, proc=proc, want_lp=with_lp)
+                if with_lp:
+                    self.stats["logprob_steps"] += 1
+                    tok, vals = tok
             else:
-                tok = self._sample_rows(logits, *self._sampling_tensors(seqs), proc=proc).tolist()
+                lp = self._lp_block(seqs)
+                tok = self._sample_rows(logits, *self._sampling_tensors(seqs), proc=proc, lp=lp).tolist()
+                if lp is not None:
+                    vals = self._lp_values(lp["buf"], n, seqs)
             if self._kernel_fault():
                 self._recover_engine_fault([dict(seqs=seqs)])
                 self.stats["decode_s"] += time.perf_counter() - t0
                 return finished
         for s in seqs:
             s.computed = s.length
-        for s, t in zip(seqs, tok):
-            r = self._accept(s, t)
+        for i, (s, t) in enumerate(zip(seqs, tok)):
+            r = self._accept(s, t, vals[i] if vals is not None else None)
             if r:
                 self._finish(s, r)
                 finished.append(s)

@@ -89,6 +89,10 @@ _SIGS = {
     "ragk_logits_proc_max_hist": [],
     "ragk_hist_write": [P, P, P, P, I, I, I, S],
     "ragk_logits_process": [P, I, I, I, I, P, P, P, P, I, I, P, P, P, I, P, S],
+    # csrc/kernels/logprobs.hip (per-token log-probabilities with top-N alternatives)
+    "ragk_logprobs_max": [],
+    "ragk_lse_partials": [P, I, I, I, I, P, S],
+    "ragk_logprobs_finish": [P, I, P, P, I, I, I, P, P, P, P, P, P, S],
     "ragk_l2_scan_groups": [I, I, I],
     "ragk_l2_search_groups": [I, I, I, I, I],
     "ragk_l2_search_set_mfma_min_nq": [I],

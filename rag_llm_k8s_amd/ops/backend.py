@@ -262,6 +262,15 @@ class TorchBackend:
     def logits_process(self, logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, ban_ids, ban_count):
         return R.logits_process(logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, ban_ids, ban_count)
 
+    # per-token log-probabilities: lse partials per vocab chunk, then the per-row merge -----------------
+    def lse_partials(self, logits, chunks, out=None):
+        return R.lse_partials(logits, chunks, out=out)
+
+    def logprobs_finish(self, part, cand_v, cand_i, list_len, tok, nlp, out_lse=None, out_tok_lp=None,
+                        out_top_lp=None, out_top_id=None):
+        return R.logprobs_finish(part, cand_v, cand_i, list_len, tok, nlp, out_lse, out_tok_lp, out_top_lp,
+                                 out_top_id)
+
     def sample_candidates(self, cand_v, cand_i, temps, top_ks, top_ps, seeds, steps, list_len=None):
         out = torch.empty(cand_v.shape[0], dtype=torch.int32)
         for b in range(cand_v.shape[0]):
@@ -429,6 +438,14 @@ class NativeBackend(TorchBackend):
 
     def logits_process(self, logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, ban_ids, ban_count):
         return self.n.logits_process(logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, ban_ids, ban_count)
+
+    def lse_partials(self, logits, chunks, out=None):
+        return self.n.lse_partials(logits, chunks, out=out)
+
+    def logprobs_finish(self, part, cand_v, cand_i, list_len, tok, nlp, out_lse=None, out_tok_lp=None,
+                        out_top_lp=None, out_top_id=None):
+        return self.n.logprobs_finish(part, cand_v, cand_i, list_len, tok, nlp, out_lse, out_tok_lp, out_top_lp,
+                                      out_top_id)
 
     def sample_candidates(self, cand_v, cand_i, temps, top_ks, top_ps, seeds, steps, list_len=None):
         return self.n.sample_candidates(cand_v, cand_i, temps, top_ks, top_ps, seeds, steps, list_len=list_len)

@@ -1466,6 +1466,77 @@ def logits_process(logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, b
     return logits
 
 
+# ----------------------------------------------------------------------------- logprobs
+from .reference import LOGPROBS_MAX, LSE_MAX_PARTS, lse_chunks  # noqa: E402,F401  (one definition, both backends)
+
+
+def _f32_buf(t, shape, dev, name):
+    _req(isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_cuda and t.device == dev
+         and tuple(t.shape) == tuple(shape) and t.is_contiguous(),
+         "%s must be a contiguous fp32 %s tensor on the launch device" % (name, list(shape)))
+
+
+def lse_partials(logits, chunks, out=None):
+    """part [B, chunks, 2] fp32 = (max, sum exp(x - max)) of every vocab chunk of fp32 logits [B, V]: rows may be
+    a strided view (any pitch >= V, any alignment: the kernel reads a scalar head / tail around the 16-byte
+    body). Chunk width as the candidate top-k's (reference.lse_chunk_width)."""
+    _req(isinstance(logits, torch.Tensor) and logits.dtype == torch.float32 and logits.is_cuda and logits.dim() == 2
+         and logits.stride(1) == 1, "logits must be fp32 [B, V] GPU rows with unit column stride")
+    B, V = logits.shape
+    _req(V >= 1 and B <= 65535 and (B <= 1 or logits.stride(0) >= V), "logits rows must not overlap")
+    _req(logits.data_ptr() % 4 == 0, "logits must be 4-byte aligned")
+    chunks = int(chunks)
+    _req(1 <= chunks <= 64, "1 <= chunks <= 64")
+    if out is None:
+        out = torch.empty((B, chunks, 2), dtype=torch.float32, device=logits.device)
+    _f32_buf(out, (B, chunks, 2), logits.device, "part")
+    check(_lib.lib().ragk_lse_partials(logits.data_ptr(), logits.stride(0) if B > 1 else max(V, logits.stride(0)), B,
+                                       V, chunks, out.data_ptr(), stream_ptr()), "ragk_lse_partials")
+    return out
+
+
+def logprobs_finish(part, cand_v, cand_i, list_len, tok, nlp, out_lse=None, out_tok_lp=None, out_top_lp=None,
+                    out_top_id=None):
+    """reference.logprobs_finish on the GPU, one four-wave workgroup per row: lse from the partials [B, P, 2] (P = every chunk
+    of every TP rank, rank-major), the sampled token's logprob from the candidate lists, and the top nlp[b]
+    alternatives into slots 0..nlp[b]-1 of out_top_id / out_top_lp [B, LOGPROBS_MAX]. Buffers that are not
+    given are allocated filled with NaN / -1 (what the kernel leaves untouched stays that)."""
+    _req(isinstance(cand_v, torch.Tensor) and cand_v.dtype == torch.float32 and cand_v.is_cuda and cand_v.dim() == 2
+         and cand_v.is_contiguous(), "cand_v must be a contiguous fp32 [B, n] GPU tensor")
+    B, n = cand_v.shape
+    dev = cand_v.device
+    _req(isinstance(cand_i, torch.Tensor) and cand_i.dtype == torch.int32 and cand_i.device == dev
+         and cand_i.shape == cand_v.shape and cand_i.is_contiguous(), "cand_i must be a contiguous int32 [B, n] tensor")
+    list_len = int(list_len)
+    _req(list_len >= LOGPROBS_MAX, "candidate lists must hold at least LOGPROBS_MAX = %d entries (got %d)"
+         % (LOGPROBS_MAX, list_len))
+    _req(n >= 1 and n % list_len == 0, "candidates must be whole lists of list_len")
+    _req(isinstance(part, torch.Tensor) and part.dim() == 3 and part.shape[0] == B and part.shape[2] == 2
+         and 1 <= part.shape[1] <= LSE_MAX_PARTS, "part must be [B, 1..%d, 2]" % LSE_MAX_PARTS)
+    _f32_buf(part, part.shape, dev, "part")
+    _i32_vec(tok, B, dev, "tok")
+    _i32_vec(nlp, B, dev, "nlp")
+    if out_lse is None:
+        out_lse = torch.full((B,), float("nan"), dtype=torch.float32, device=dev)
+    if out_tok_lp is None:
+        out_tok_lp = torch.full((B,), float("nan"), dtype=torch.float32, device=dev)
+    if out_top_lp is None:
+        out_top_lp = torch.full((B, LOGPROBS_MAX), float("nan"), dtype=torch.float32, device=dev)
+    if out_top_id is None:
+        out_top_id = torch.full((B, LOGPROBS_MAX), -1, dtype=torch.int32, device=dev)
+    _f32_buf(out_lse, (B,), dev, "out_lse")
+    _f32_buf(out_tok_lp, (B,), dev, "out_tok_lp")
+    _f32_buf(out_top_lp, (B, LOGPROBS_MAX), dev, "out_top_lp")
+    _req(out_top_id.dtype == torch.int32 and out_top_id.is_cuda and out_top_id.device == dev
+         and tuple(out_top_id.shape) == (B, LOGPROBS_MAX) and out_top_id.is_contiguous(),
+         "out_top_id must be a contiguous int32 [B, %d] tensor on the launch device" % LOGPROBS_MAX)
+    check(_lib.lib().ragk_logprobs_finish(part.data_ptr(), part.shape[1], cand_v.data_ptr(), cand_i.data_ptr(), B, n,
+                                          list_len, tok.data_ptr(), nlp.data_ptr(), out_lse.data_ptr(),
+                                          out_tok_lp.data_ptr(), out_top_lp.data_ptr(), out_top_id.data_ptr(),
+                                          stream_ptr()), "ragk_logprobs_finish")
+    return out_lse, out_tok_lp, out_top_lp, out_top_id
+
+
 # ----------------------------------------------------------------------------- search
 def l2_search_set_mfma_min_nq(n):
     """Batches of at least n queries (k <= 8, d % 32 == 0) take the MFMA ||x||^2+||q||^2-2x.q path."""

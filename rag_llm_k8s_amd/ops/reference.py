@@ -303,6 +303,100 @@ def logits_process(logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, b
     return logits
 
 
+LOGPROBS_MAX = 20  # alternatives per generated position (csrc/kernels/logprobs.hip LP_MAX)
+LSE_MAX_PARTS = 512  # partials per row the finish kernel folds: 64 chunks x 8 tensor-parallel ranks
+LSE_SMALL_BATCH_MAX_B = 64
+LSE_SMALL_BATCH_CHUNK = 4096
+LSE_CHUNK = 16384
+
+
+def lse_chunks(V, B):
+    """Workgroups per row of lse_partials, from the PADDED shard width V (every TP rank: the same count): ~4k
+    logits each up to batch 64 (a 128k vocabulary at batch 1 spreads over 31 CUs), ~16k above; 1..64."""
+    return max(1, min(V // (LSE_SMALL_BATCH_CHUNK if B <= LSE_SMALL_BATCH_MAX_B else LSE_CHUNK), 64))
+
+
+def lse_chunk_width(V, chunks):
+    """Entries per chunk (the candidate top-k's rule): ceil(V / chunks) rounded up to a multiple of 8."""
+    return ((V + chunks - 1) // chunks + 7) & ~7
+
+
+def lse_partials(logits, chunks, out=None):
+    """part[b, c] = (m, s): m = max and s = sum exp(x - m) over logits[b, c * Vc : min((c + 1) * Vc, V)], fp32.
+    A chunk that is empty or all -inf gives (-inf, 0)."""
+    B, V = logits.shape
+    if not 1 <= chunks <= 64:
+        raise ValueError("1 <= chunks <= 64")
+    Vc = lse_chunk_width(V, chunks)
+    part = torch.empty((B, chunks, 2), dtype=torch.float32) if out is None else out
+    x = logits.float()
+    for c in range(chunks):
+        seg = x[:, min(c * Vc, V):min((c + 1) * Vc, V)]
+        if seg.shape[1] == 0:
+            part[:, c, 0], part[:, c, 1] = float("-inf"), 0.0
+            continue
+        m = seg.max(1).values
+        ok = m > float("-inf")
+        s = torch.exp(seg - torch.where(ok, m, torch.zeros_like(m))[:, None]).sum(1)
+        part[:, c, 0] = m
+        part[:, c, 1] = torch.where(ok, s, torch.zeros_like(s))
+    return part
+
+
+def lse_from_partials(part):
+    """lse[b] = M + log(S), M = max_p m_p, S = sum over ascending p of s_p * exp(m_p - M) (m_p = -inf adds 0)."""
+    m, s = part[..., 0].float(), part[..., 1].float()
+    M = m.max(1).values
+    S = torch.zeros_like(M)
+    for p in range(m.shape[1]):
+        dead = m[:, p] == float("-inf")
+        e = torch.exp(torch.where(dead, torch.zeros_like(M), m[:, p] - M))
+        S = S + torch.where(dead, torch.zeros_like(M), s[:, p] * e)
+    return M + torch.log(S)
+
+
+def logprobs_finish(part, cand_v, cand_i, list_len, tok, nlp, out_lse=None, out_tok_lp=None, out_top_lp=None,
+                    out_top_id=None):
+    """Per-row log-probabilities from the lse partials [B, P, 2] and the candidate lists the sampler got
+    (cand_v / cand_i [B, n] = n / list_len sorted lists): row b with N = nlp[b] >= 0 gets out_lse[b],
+    out_tok_lp[b] = v_j - lse for the candidate j whose id is tok[b] (NaN if there is none) and, in slots
+    0..N-1 of out_top_id / out_top_lp [B, LOGPROBS_MAX], the first N candidates by (value desc, id asc) as
+    (id, v - lse). Slots >= N and rows with nlp < 0 are left untouched."""
+    B, n = cand_v.shape
+    if list_len < LOGPROBS_MAX or n % list_len:
+        raise ValueError("logprobs_finish: candidate lists of at least %d entries" % LOGPROBS_MAX)
+    if not 1 <= part.shape[1] <= LSE_MAX_PARTS:
+        raise ValueError("logprobs_finish: 1..%d partials per row" % LSE_MAX_PARTS)
+    nan = float("nan")
+    out_lse = torch.full((B,), nan) if out_lse is None else out_lse
+    out_tok_lp = torch.full((B,), nan) if out_tok_lp is None else out_tok_lp
+    out_top_lp = torch.full((B, LOGPROBS_MAX), nan) if out_top_lp is None else out_top_lp
+    out_top_id = torch.full((B, LOGPROBS_MAX), -1, dtype=torch.int32) if out_top_id is None else out_top_id
+    lse = lse_from_partials(part)
+    for b in range(B):
+        N = min(int(nlp[b]), LOGPROBS_MAX)
+        if N < 0:
+            continue
+        out_lse[b] = lse[b]
+        v, i = cand_v[b].float(), cand_i[b].long()
+        t = int(tok[b])
+        hit = (i == t).nonzero().flatten() if t >= 0 else i[:0]
+        out_tok_lp[b] = v[hit[0]] - lse[b] if hit.numel() else nan
+        if N == 0:
+            continue
+        # only the first N of each sorted list can qualify; padding (id -1) sorts last
+        head = (torch.arange(n) % list_len) < N
+        hv, hi = v[head], i[head]
+        hv = torch.where(hi >= 0, hv, torch.full_like(hv, float("-inf")))
+        key = torch.where(hi >= 0, hi, torch.full_like(hi, 1 << 32))
+        o = torch.argsort(key, stable=True)
+        o = o[torch.argsort(hv[o], descending=True, stable=True)][:N]
+        k = o.numel()
+        out_top_id[b, :k] = hi[o].to(out_top_id.dtype)
+        out_top_lp[b, :k] = hv[o] - lse[b]
+    return out_lse, out_tok_lp, out_top_lp, out_top_id
+
+
 def l2_knn(xb, q, k):
     """faiss IndexFlatL2.search: squared L2, ascending; pad (-1, FLT_MAX)."""
     n = xb.shape[0]

@@ -197,6 +197,17 @@ class TPComm:
         return gv.permute(1, 0, 2).reshape(B, self.size * K).contiguous(), \
             gi.permute(1, 0, 2).reshape(B, self.size * K).contiguous()
 
+    def gather_partials(self, part: torch.Tensor):
+        """Vocab-parallel logprob exchange: per-rank lse partials [B, C, 2] (fp32) -> [B, size*C, 2], rank-major
+        within a row (identical on every rank); travels like the candidates."""
+        B, C, _ = part.shape
+        if self.size == 1:
+            return part
+        x = part.contiguous().view(torch.int32).reshape(B, C * 2)
+        g = torch.empty((self.size * B, C * 2), dtype=torch.int32, device=part.device)
+        self.all_gather_into(g, x)
+        return g.view(torch.float32).view(self.size, B, C, 2).permute(1, 0, 2, 3).reshape(B, self.size * C, 2).contiguous()
+
     def reduce_scatter(self, x: torch.Tensor, out: torch.Tensor = None):
         """Sum of every rank's x [size*S, ...], this rank's S-row slice: RCCL reduce-scatter (each
         byte crosses xGMI once, half an all-reduce); gloo has none -- fp32 all-reduce + slice."""

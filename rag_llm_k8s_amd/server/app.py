@@ -16,6 +16,12 @@ New (documents can be listed, removed, replaced and filtered on; the reference c
   POST /generate     optional "repetition_penalty": float > 0, "no_repeat_ngram_size": 0..8, "min_new_tokens":
                      0..MAX_NEW_TOKENS -> override REPETITION_PENALTY / NO_REPEAT_NGRAM_SIZE / MIN_NEW_TOKENS for
                      this request (transformers' generate() semantics); a refused value -> 400 {"error"}
+  POST /generate     optional "logprobs": N (integer 0..20; overrides LOGPROBS) -> the response gains "logprobs":
+                     {"token_ids", "tokens", "token_logprobs", "top_logprobs": [[{"id", "token", "logprob"}, ...],
+                     ...], "mean_logprob"} over every generated token (a final eos included): log_softmax of the
+                     fp32 logits after the logit processors, before temperature / top-k / top-p, with the N most
+                     likely alternatives per position; a bool, float, negative or > 20 value -> 400 {"error"}.
+                     Without the field (and without LOGPROBS) the response keys are unchanged
   POST /upload_pdf?replace=1 (or form field replace=1) -> the document's old chunks are replaced
   GET  /documents    -> {"documents": [{"filename", "chunks"}]}
   DELETE /documents/<filename> -> 200 {"message", "chunks_removed"} | 404 {"error"}

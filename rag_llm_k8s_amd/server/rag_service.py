@@ -283,7 +283,8 @@ class RagService:
                                      ignore_eos=bool(getattr(cfg, "ignore_eos", False)),
                                      repetition_penalty=float(getattr(cfg, "repetition_penalty", 1.0)),
                                      no_repeat_ngram_size=int(getattr(cfg, "no_repeat_ngram_size", 0)),
-                                     min_new_tokens=int(getattr(cfg, "min_new_tokens", 0)))
+                                     min_new_tokens=int(getattr(cfg, "min_new_tokens", 0)),
+                                     logprobs=getattr(cfg, "logprobs", None))
         llm_engine.check_params(self.params)
         self.loop = EngineLoop(llm_engine, control=control)
         # tensor-parallel group (set by the TP server): PDF ingest is data-parallel over it and, with
@@ -425,9 +426,23 @@ class RagService:
             ids = ids[len(ids) - limit:]  # keep the question and "Chatbot:" suffix
         return ids
 
-    # per-request logit-processor fields of /generate (JSON names = SamplingParams names) and their JSON types
+    # per-request sampling fields of /generate (JSON names = SamplingParams names) and their JSON types: the
+    # logit processors, and "logprobs": N (0..20) for per-token log-probabilities with N alternatives
     REQUEST_PARAM_FIELDS = {"repetition_penalty": (int, float), "no_repeat_ngram_size": (int,),
-                            "min_new_tokens": (int,)}
+                            "min_new_tokens": (int,), "logprobs": (int,)}
+
+    def logprobs_object(self, s):
+        """The "logprobs" object of a response (None for a request that did not ask): every generated token of
+        s.out, a final eos included, whatever the "Chatbot:" post-processing does to the text. Alternatives
+        whose logprob is -inf (fewer than N finite logits) are dropped."""
+        if s.logprobs is None:
+            return None
+        text = lambda t: self.tok.decode([t], skip_special_tokens=False)  # noqa: E731
+        top = [[{"id": i, "token": text(i), "logprob": lp} for i, lp in alts if lp != float("-inf")]
+               for alts in s.top_logprobs]
+        n = len(s.logprobs)
+        return {"token_ids": list(s.out), "tokens": [text(t) for t in s.out], "token_logprobs": list(s.logprobs),
+                "top_logprobs": top, "mean_logprob": (sum(s.logprobs) / n) if n else None}
 
     def request_params(self, overrides):
         """The service's default SamplingParams with a request's logit-processor fields replaced. Raises
@@ -480,6 +495,8 @@ class RagService:
         metrics.observe("request", tr.total())
         log.debug("Generated response: %s...", text[:200])
         out = {"generated_text": text, "context": context}
+        if s.logprobs is not None:
+            out["logprobs"] = self.logprobs_object(s)
         if debug:
             out["timings_ms"] = tr.summary_ms()
             out["prompt_tokens"] = len(ids)
@@ -603,6 +620,8 @@ class RagService:
             outs.append({"generated_text": text, "context": ctx, "_latency_s": s.t_done - t0,
                          "_ttft_s": (s.t_first or s.t_done) - t0, "_prompt_tokens": len(s.prompt),
                          "_gen_tokens": len(s.out)})
+            if s.logprobs is not None:
+                outs[-1]["logprobs"] = self.logprobs_object(s)
             if ret is not None:
                 outs[-1]["_retrieved"] = ret
         return outs
