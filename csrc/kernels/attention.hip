@@ -188,23 +188,15 @@ __device__ inline void prefill_block(const PrefillArgs& a, int& tile, int& hg) {
   }
 }
 
-__device__ unsigned long long* g_attn_dbg = nullptr;  // stamp build only
-
-// PRIO: wave priority around the MFMA clusters (0 none, 1 QK^T and PV, 2 PV only). Two waves share
-// each SIMD (2 blocks per CU); raising the priority of the wave that is issuing MFMAs lets the
-// other wave's softmax VALU fill around them instead of delaying them.
-// BUF (PAGED only, cache < 4 GiB): K/V tiles staged by buffer_load ... lds with the per-lane byte
-// offsets (row, swizzled chunk) computed once and the tile's cache offset in an SGPR, instead of
-// 64-bit address math per piece per tile (the stamp build put the DMA issue at ~490 of ~4300 wave
-// cycles per tile).
+// Generic flash prefill / encoder kernel: NWV waves (4, or 8 = two 32-row query groups sharing each K/V
+// tile), every wave in lockstep phases QK^T -> softmax -> PV over a double-buffered K/V tile pair; the
+// next tile's LDS-DMA is issued behind the QK^T MFMAs.
 // F8 (PAGED, D = 128): fp8 cache. K tiles by LDS-DMA in the Cfg<64> byte geometry, V tiles through registers
 // into the bf16 V layout (issued with the K DMA, converted and written after the PV MFMAs), the tile's 64 + 64
 // row scales through LDS; S *= ks[key] before the softmax, P *= vs[key] after the row sum.
-template <int D, int GB, bool CAUSAL, bool PAGED, bool STAMP = false, int NWV = 4, int PRIO = 0,
-          bool BUF = false, bool F8 = false>
+template <int D, int GB, bool CAUSAL, bool PAGED, int NWV = 4, bool F8 = false>
 __global__ __launch_bounds__(NWV * 64, 8 / NWV) void attn_prefill_kernel(PrefillArgs a) {
-  static_assert(!F8 || (PAGED && D == F8_D && !BUF), "fp8 cache: paged, D = 128");
-  unsigned long long stp[6] = {0, 0, 0, 0, 0, 0};
+  static_assert(!F8 || (PAGED && D == F8_D), "fp8 cache: paged, D = 128");
   using C = Cfg<D>;
   constexpr int NTH = NWV * 64;
   constexpr int QT = 32 * (NWV / GB);  // query positions per block
@@ -258,7 +250,7 @@ __global__ __launch_bounds__(NWV * 64, 8 / NWV) void attn_prefill_kernel(Prefill
   const int* bt = PAGED ? a.block_tables + (size_t)seq * a.bt_stride : nullptr;
 
   // the sequence's block-table row, cached in LDS once (a global load per tile sat on the DMA
-  // issue path: ~1.2k of ~5.7k wave cycles per tile in the stamp build, tools/attn_stamps.py)
+  // issue path: ~1.2k of ~5.7k wave cycles per tile when measured with cycle stamps)
   __shared__ int s_bt[PAGED ? MAX_BT : 1];
   if constexpr (PAGED) {
     for (int i = threadIdx.x; i < n_kt; i += NTH) s_bt[i] = bt[i];
@@ -266,21 +258,6 @@ __global__ __launch_bounds__(NWV * 64, 8 / NWV) void attn_prefill_kernel(Prefill
   }
   int bt_next = PAGED && n_kt > 0 ? s_bt[0] : 0;  // block of the tile staged next
 
-  static_assert(!BUF || (PAGED && C::PIECES % NWV == 0), "buffer staging: paged caches, whole pieces per wave");
-  constexpr int BPW = BUF ? C::PIECES / NWV : 1;
-  int koff[BPW], voff[BPW];
-  i32x4 srd_k, srd_v;
-  if constexpr (BUF) {
-#pragma unroll
-    for (int i = 0; i < BPW; ++i) {
-      const int p = wid_u + NWV * i;
-      const int row = p * C::RPP + lane / C::NC, ph = lane % C::NC;
-      koff[i] = row * C::ROWB + 16 * (ph ^ kswz<D>(row));
-      voff[i] = row * C::ROWB + 16 * (ph ^ vswz<D>(row));
-    }
-    srd_k = make_srd(a.k, a.kv_bytes);
-    srd_v = make_srd(a.v, a.kv_bytes);
-  }
   // F8: the V chunks and scales of the tile being staged, held in registers from stage() to commit()
   constexpr int VPT = F8 ? 512 / NTH : 1;  // 16-byte V chunks per thread
   __shared__ __attribute__((aligned(16))) float s_sc[F8 ? 4 * KT : 4];  // [buf][K | V][64]
@@ -307,15 +284,6 @@ __global__ __launch_bounds__(NWV * 64, 8 / NWV) void attn_prefill_kernel(Prefill
       for (int i = 0; i < VPT; ++i) f8_v[i] = f8_ld16<false>(vb + 16 * ((int)threadIdx.x + NTH * i));
       if (threadIdx.x < 2 * KT)
         f8_sc = (threadIdx.x < KT ? a.ks : a.vs)[blk * KT + (threadIdx.x & (KT - 1))];
-    } else if constexpr (BUF) {
-      // unsigned: a cache of 2-4 GiB has tile offsets past INT_MAX (soffset is an unsigned 32-bit add)
-      const int soff = __builtin_amdgcn_readfirstlane((int)((unsigned)(bt_next * a.Hkv + kvh) * (unsigned)(KT * D * 2)));
-#pragma unroll
-      for (int i = 0; i < BPW; ++i) {
-        const int p = wid_u + NWV * i;
-        blds16(srd_k, koff[i], soff, sK + p * 1024);
-        blds16(srd_v, voff[i], soff, sV + p * 1024);
-      }
     } else if constexpr (PAGED) {
       const size_t base = ((size_t)bt_next * a.Hkv + kvh) * KT * D;
       const bf16_t* kb = a.k + base;
@@ -343,8 +311,6 @@ __global__ __launch_bounds__(NWV * 64, 8 / NWV) void attn_prefill_kernel(Prefill
   __syncthreads();
 
   for (int kt = 0; kt < n_kt; ++kt) {
-    unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0;
-    if constexpr (STAMP) t0 = __builtin_amdgcn_s_memtime();
     const int cur = kt & 1;
     const char* sK = smem + cur * 2 * C::TILEB;
     const char* sV = sK + C::TILEB;
@@ -353,7 +319,6 @@ __global__ __launch_bounds__(NWV * 64, 8 / NWV) void attn_prefill_kernel(Prefill
     // ---- S^T = K Q^T ----
     f32x4 s[4][2];
     if (active) {
-      if constexpr (PRIO == 1) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         s[t][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -372,14 +337,11 @@ __global__ __launch_bounds__(NWV * 64, 8 / NWV) void attn_prefill_kernel(Prefill
           s[t][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[1][ks], s[t][1], 0, 0, 0);
         }
       }
-      if constexpr (PRIO == 1) __builtin_amdgcn_s_setprio(0);
     }
-    if constexpr (STAMP) t1 = __builtin_amdgcn_s_memtime();
     // next tile's DMA issued behind the QK^T MFMAs (async-STAGE split: the issue overlaps the MFMA
     // pipe instead of delaying it); every wave stages its pieces, active or not
     if (kt + 1 < n_kt) stage(kt + 1, cur ^ 1);
     if constexpr (PAGED) bt_next = kt + 2 < n_kt ? s_bt[kt + 2] : 0;  // consumed next iteration
-    if constexpr (STAMP) t2 = t3 = t4 = __builtin_amdgcn_s_memtime();
     if (active) {
       f32x4 vsc[4];  // F8: V row scales of this lane's 16 keys
       if constexpr (F8) {
@@ -462,8 +424,6 @@ __global__ __launch_bounds__(NWV * 64, 8 / NWV) void attn_prefill_kernel(Prefill
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) pb[ks][qt] = pack_p(s[2 * ks][qt], s[2 * ks + 1][qt]);
-      if constexpr (STAMP) t3 = __builtin_amdgcn_s_memtime();
-      if constexpr (PRIO != 0) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int dt = 0; dt < C::DT; ++dt)
 #pragma unroll
@@ -472,28 +432,10 @@ __global__ __launch_bounds__(NWV * 64, 8 / NWV) void attn_prefill_kernel(Prefill
           o[dt][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pb[ks][0], o[dt][0], 0, 0, 0);
           o[dt][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pb[ks][1], o[dt][1], 0, 0, 0);
         }
-      if constexpr (PRIO != 0) __builtin_amdgcn_s_setprio(0);
-      if constexpr (STAMP) t4 = __builtin_amdgcn_s_memtime();
     }
     if (kt + 1 < n_kt) commit(cur ^ 1);
     wait_vmcnt0();
     __syncthreads();
-    if constexpr (STAMP) {
-      const unsigned long long t5 = __builtin_amdgcn_s_memtime();
-      stp[0] += t2 - t1;  // DMA issue of the next tile
-      stp[1] += t1 - t0;  // QK^T (K reads + 32 MFMA issue)
-      stp[2] += t3 - t2;  // softmax (+ waiting for the QK^T results)
-      stp[3] += t4 - t3;  // PV (V tr-reads + 32 MFMA issue)
-      stp[4] += t5 - t4;  // vmcnt(0) + barrier
-      stp[5] += 1;
-    }
-  }
-  if constexpr (STAMP) {
-    if (lane == 0 && g_attn_dbg) {
-      unsigned long long* d = g_attn_dbg + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + wid) * 6;
-#pragma unroll
-      for (int i = 0; i < 6; ++i) d[i] = stp[i];
-    }
   }
 
   // ---- finalize: O = O^T / l, store 4 consecutive d (8 B) per (dt, qt) ----
@@ -528,22 +470,21 @@ __device__ __forceinline__ void pp_static_for(F&& f) {
 }
 
 // ------------------------------------------------------------------------------------
-// Software-pipelined prefill attention, one wave per SIMD (Llama config: D 128, 4 query heads per
-// KV head, causal, paged cache < 4 GiB). attn_prefill_kernel runs two waves per SIMD, each in
-// lockstep phases QK^T -> softmax -> PV: the stamps put a wave at ~4.3k cycles per 64-key tile for
-// 1024 cycles of its own 16x16x32 MFMAs (~48 % matrix-pipe use), and a barrier-alternated 8-wave
-// variant (attn_prefill_pp_kernel) was slower still -- the two waves of a SIMD share one vector
-// issue port, and a 16x16x32 MFMA holds it 8 of its 16 cycles. Here:
+// Software-pipelined prefill attention (Llama config: D 128, 4 query heads per KV head, causal, paged
+// cache < 4 GiB). attn_prefill_kernel runs every wave in lockstep phases QK^T -> softmax -> PV: measured
+// with cycle stamps, a wave took ~4.3k cycles per 64-key tile for 1024 cycles of its own 16x16x32 MFMAs
+// (~48 % matrix-pipe use) -- the two waves of a SIMD share one vector issue port, and a 16x16x32 MFMA
+// holds it 8 of its 16 cycles. Here:
 //   * 32x32x16 MFMAs (the issue port is held 8 of 32 cycles per MFMA, MI355X_MICROARCH.md cycle
-//     constants), 32 per tile per wave, and ONE wave per SIMD (4-wave block, one block per CU);
+//     constants), 32 per tile per wave;
 //   * iteration t issues PV(t-1) then QK^T(t+1) on the matrix pipe while the same wave's VALU runs the
-//     online softmax of tile t between them: 32 slots, one MFMA each, the LDS fragment of slot i + 2
+//     online softmax of tile t between them: 32 slots, one MFMA each, the LDS fragment of slot i + V3_PF
 //     and a softmax chunk (max in slots 0..3, row statistics in 4, one element's fma / exp / add per
-//     slot from 5 on: at most one transcendental per MFMA gap). Every MFMA is an ordered volatile asm
-//     and each chunk's inputs / results are pinned, so neither the IR passes nor the scheduler can
-//     regroup the stream; S is double-buffered (tile loop unrolled by two), P is single-buffered
+//     slot from 5 on: at most one transcendental per MFMA gap). A scheduling barrier closes every slot
+//     and each chunk's results are pinned, so neither the IR passes nor the scheduler can regroup the
+//     stream; S is double-buffered (S0 / S1 alternate over the unrolled tile loop), P is single-buffered
 //     (P(t-1)[ks] is dead before P(t)[ks] is packed);
-//   * K / V ring of 4 slots, K staged 3 and V 2 tiles ahead, so iteration t's last two slots can read
+//   * K / V ring of 4 slots, K staged 3 and V 2 tiles ahead, so iteration t's last V3_PF slots can read
 //     the first PV fragments of iteration t + 1; LDS-DMA as inline asm (the intrinsic made the
 //     waitcnt pass drain vmcnt(0) before every later ds_read); one vmcnt + barrier per tile.
 // Diagonal / ragged tiles (masked softmax), the first tile (no PV) and the last (no QK) run the same
@@ -574,10 +515,6 @@ template <typename T>
 __device__ __forceinline__ void pin(T& x) {
   asm volatile("" : "+v"(x));
 }
-__device__ __forceinline__ void pin_s(int& x) { asm volatile("" : "+s"(x)); }
-// The asm MFMAs are opaque to the compiler's hazard recognizer: a VALU read of an MFMA result needs
-// the XDL-write -> VALU-read wait states (18 for a 16-pass op), and a VALU write read by an MFMA a few.
-__device__ __forceinline__ void mfma_result_wait() {}
 // LDS-DMA piece as inline asm: the compiler's waitcnt pass cannot tell which LDS bytes a
 // buffer_load ... lds intrinsic writes, so it drained vmcnt(0) before the next ds_read of ANY slot
 // (an HBM round trip per fragment read). The kernel orders its slots itself (vmcnt + barrier per
@@ -590,17 +527,15 @@ __device__ __forceinline__ unsigned lds_addr(const void* p) {
   return (unsigned)(unsigned long long)(const __attribute__((address_space(3))) char*)p;
 }
 
-// NW = 8: two groups of 4 waves (query rows q_start + [0, 32) and + [32, 64)) share every K / V tile,
-// so each SIMD runs two of these streams and one wave's dependency stalls are the other's issue slots.
-// DIAG (stamp builds only, wrong results): 1 = no softmax chunks in the fast slots, 2 = no fragment reads
-// PRIO_B: static s_setprio 1 for waves 4-7 over the tile loop (MI355X_MICROARCH.md "Two waves per SIMD"
-// item 4: the second-dispatched half loses every arbitration otherwise).
-// WIDE: the output tile goes through LDS and out as whole 256-B rows (16-B stores, 4 rows per wave
-// instruction) instead of 16 8-B stores per lane into 32 different rows (MI355X_MICROARCH.md: the
-// attention epilogue store tail is store-issue bound).
-template <int NW = 4, bool STAMP = false, int DIAG = 0, int PRIO_B = 0, bool WIDE = false>
-__global__ __launch_bounds__(NW * 64, NW / 4) void attn_prefill_v3_kernel(PrefillArgs a) {
-  constexpr int D = 128;
+// 8 waves: two groups of 4 (query rows q_start + [0, 32) and + [32, 64)) share every K / V tile, so each
+// SIMD runs two of these streams and one wave's dependency stalls are the other's issue slots.
+// Waves 4-7 run the tile loop at static s_setprio 1 (MI355X_MICROARCH.md "Two waves per SIMD" item 4: the
+// second-dispatched half loses every arbitration otherwise).
+// The output tile goes through LDS and out as whole 256-B rows (16-B stores, 4 rows per wave instruction)
+// instead of 16 8-B stores per lane into 32 different rows (MI355X_MICROARCH.md: the attention epilogue
+// store tail is store-issue bound).
+__global__ __launch_bounds__(512, 2) void attn_prefill_v3_kernel(PrefillArgs a) {
+  constexpr int D = 128, NW = 8;
   using C = Cfg<D>;
   __shared__ __attribute__((aligned(16))) char smem[2 * V3_NS * C::TILEB];  // [K slots][V slots] 128 KB
   __shared__ int s_bt[MAX_BT];
@@ -780,7 +715,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void attn_prefill_v3_kernel(Prefil
     __builtin_amdgcn_sched_barrier(0);
   };
 
-  unsigned long long stp[4] = {0, 0, 0, 0};
   // Fast iteration t (1 <= t < t_end: tile t unmasked, PV(t-1) and QK^T(t+1) exist). MFMA slots
   // 0..15: PV(t-1) (V slot t-1; ks = i / 4, db = i % 4), 16..31: QK^T(t+1) (K slot t+1; kb = i % 2,
   // d-step (i-16) / 2). Slot i reads the fragment of slot i + V3_PF; the last V3_PF slots read the
@@ -792,8 +726,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void attn_prefill_v3_kernel(Prefil
   // profiles/attn_prefill_unroll4_ab_r5.log)
   auto fast = [&](auto ph_tag, int t, f32x16 (&S_cur)[2], f32x16 (&S_next)[2]) {
     constexpr int PH = decltype(ph_tag)::value;
-    unsigned long long t0 = 0;
-    if constexpr (STAMP) t0 = __builtin_amdgcn_s_memtime();
     static_assert(V3_NS == 4 && PH >= 0 && PH < 4, "slot phase");
     constexpr int vo = (V3_NS + ((PH + 3) & 3)) * C::TILEB;  // V(t - 1)
     constexpr int ko = ((PH + 1) & 3) * C::TILEB;            // K(t + 1)
@@ -816,15 +748,12 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void attn_prefill_v3_kernel(Prefil
       // fragment for slot i + V3_PF (the per-lane bases x tile offsets are CSE'd: 12 address adds per
       // iteration; the scheduling barrier at the end of the slot keeps each read in its slot)
       constexpr int j = i + V3_PF;
-      if constexpr (DIAG != 2) {
-        const int ao = j < 16 ? vo : (j < 32 ? ko : vno);
-        if constexpr (j < 16) ring[j % V3_RING] = vfrag(ao, j % 4, j / 4);
-        else if constexpr (j < 32) ring[j % V3_RING] = kfrag(ao, j % 2, (j - 16) / 2);
-        else ring[j % V3_RING] = vfrag(ao, (j - 32) % 4, (j - 32) / 4);
-      }
+      const int ao = j < 16 ? vo : (j < 32 ? ko : vno);
+      if constexpr (j < 16) ring[j % V3_RING] = vfrag(ao, j % 4, j / 4);
+      else if constexpr (j < 32) ring[j % V3_RING] = kfrag(ao, j % 2, (j - 16) / 2);
+      else ring[j % V3_RING] = vfrag(ao, (j - 32) % 4, (j - 32) / 4);
       // softmax chunk: max in slots 0..3, row statistics in 4, one element per slot from 5 on
-      if constexpr (DIAG == 1) {
-      } else if constexpr (i < 4) {
+      if constexpr (i < 4) {
         // no input pins: a pinned copy of each element cost a v_mov (the sched barrier keeps the slot)
 #pragma unroll
         for (int e = 0; e < 8; ++e) mx = fmaxf(mx, S_cur[i / 2][8 * (i % 2) + e]);
@@ -870,33 +799,17 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void attn_prefill_v3_kernel(Prefil
       __builtin_amdgcn_sched_barrier(0);
     });
     l_i = l_i * alpha + (ls + pend);
-    if constexpr (STAMP) {
-      const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-      stp[0] += t1 - t0;
-      t0 = t1;
-    }
     rescale(alpha);
-    // this iteration's DMAs (PPW per issued tile) stay in flight, the previous iteration's have landed
-    if constexpr (PPW == 4) {
-      if (st_k && st_v) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else if (st_k || st_v) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else wait_vmcnt0();
-    } else {
-      if (st_k && st_v) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else if (st_k || st_v) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-      else wait_vmcnt0();
-    }
+    // this iteration's DMAs (PPW = 2 per issued tile) stay in flight, the previous iteration's have landed
+    static_assert(PPW == 2, "vmcnt counts below");
+    if (st_k && st_v) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    else if (st_k || st_v) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+    else wait_vmcnt0();
     barrier();
-    if constexpr (STAMP) stp[1] += __builtin_amdgcn_s_memtime() - t0;
   };
 
-  unsigned long long te = 0;
-  if constexpr (STAMP) te = __builtin_amdgcn_s_memtime();
-  if constexpr (PRIO_B) {
-    if (wid_u >= 4) __builtin_amdgcn_s_setprio(1);
-  }
+  if (wid_u >= 4) __builtin_amdgcn_s_setprio(1);
   qk_simple(0, S0);  // S(0)
-  mfma_result_wait();
   // fast iterations: [1, t_end); warm-up tile 0 when there is at least one
   const int t_end = min(n_fast, n_kt - 1);
   int t = 0;
@@ -904,7 +817,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void attn_prefill_v3_kernel(Prefil
     // tile 0 (unmasked, QK^T(1) exists): softmax(0), S(1), DMA K(3) / V(2), the first PV(0) fragments
     softmax(std::false_type{}, 0, S0);
     qk_simple(1, S1);
-    mfma_result_wait();
     if (3 < n_kt) stage(3, false);
     if (2 < n_kt) stage(2, true);
 #pragma unroll
@@ -938,11 +850,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void attn_prefill_v3_kernel(Prefil
       for (int kb = 0; kb < 2; ++kb) S0[kb] = S1[kb];
     }
   }
-  if constexpr (STAMP) {
-    const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-    stp[2] += t1 - te - stp[0] - stp[1];
-    te = t1;
-  }
   // epilogue: tiles [t, n_kt) (masked diagonal / ragged ones and the last; at most 3), S(t) in S0, P(t-1)
   // pending. Every tile they touch is staged after V(t + 2) here (the ring holds it), then drained.
   if (t + 2 < n_kt) stage(t + 2, true);
@@ -952,64 +859,38 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void attn_prefill_v3_kernel(Prefil
   for (; t < n_kt; ++t) {
     const int k0 = t * KT;
     const bool need_mask = (k0 + KT - 1 > ctx0 + pbase) || (k0 + KT > kv_len);
-    mfma_result_wait();  // S(t) and O from the MFMAs just issued
     const float alpha = need_mask ? softmax(std::true_type{}, k0, S0) : softmax(std::false_type{}, k0, S0);
     rescale(alpha);
     pv_simple(t);
     if (t + 1 < n_kt) qk_simple(t + 1, S0);
-  }
-  if constexpr (STAMP) stp[3] += __builtin_amdgcn_s_memtime() - te;
-  if constexpr (STAMP) {
-    if (lane == 0 && g_attn_dbg) {
-      unsigned long long* d = g_attn_dbg + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * NW + wid_u) * 6;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) d[i] = stp[i];
-      d[4] = n_kt;
-      d[5] = max(0, min(n_fast, n_kt - 1) - 1);  // fast iterations
-    }
   }
 
   // finalize: O^T[32 db + 8 b + 4 h + r][query] = o[db][4 b + r] / l; {r0, r1} = {l_i, partner's l_i}
   const auto lr = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_i), __float_as_uint(l_i), false, false);
   const float l = __uint_as_float(lr[0]) + __uint_as_float(lr[1]);
   const float inv = l > 0.f ? 1.f / l : 0.f;
-  const int qi = pbase + l32;
-  if constexpr (WIDE) {
-    // every wave is past its last K / V slot read (the loop's barrier count is the same in both groups),
-    // so the ring is free: each wave stages its 32 x 128 bf16 tile (8 KiB, rows of 256 B, 16-B chunk c of
-    // row r at slot c ^ (r & 15)) and stores whole rows
-    __syncthreads();
-    char* so = smem + wid_u * 8192;
+  // every wave is past its last K / V slot read (the loop's barrier count is the same in both groups),
+  // so the ring is free: each wave stages its 32 x 128 bf16 tile (8 KiB, rows of 256 B, 16-B chunk c of
+  // row r at slot c ^ (r & 15)) and stores whole rows
+  __syncthreads();
+  char* so = smem + wid_u * 8192;
 #pragma unroll
-    for (int db = 0; db < 4; ++db)
+  for (int db = 0; db < 4; ++db)
 #pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const int e = 4 * b;
-        const int d = 32 * db + 8 * b + 4 * h;  // 4 values: chunk d / 8, half (d / 4) & 1
-        const int c = (d >> 3) ^ (l32 & 15);
-        *reinterpret_cast<uint2*>(so + l32 * 256 + 16 * c + 8 * ((d >> 2) & 1)) =
-            make_uint2(pk2bf(o[db][e] * inv, o[db][e + 1] * inv), pk2bf(o[db][e + 2] * inv, o[db][e + 3] * inv));
-      }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the wave's own LDS writes, read back by itself
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int r = 4 * i + (lane >> 4), c = lane & 15;
-      const u32x4 v = *reinterpret_cast<const u32x4*>(so + r * 256 + 16 * (c ^ (r & 15)));
-      if (pbase + r < q_len)
-        *reinterpret_cast<u32x4*>(a.out + (size_t)(q_off + pbase + r) * a.out_stride + hq * D + 8 * c) = v;
+    for (int b = 0; b < 4; ++b) {
+      const int e = 4 * b;
+      const int d = 32 * db + 8 * b + 4 * h;  // 4 values: chunk d / 8, half (d / 4) & 1
+      const int c = (d >> 3) ^ (l32 & 15);
+      *reinterpret_cast<uint2*>(so + l32 * 256 + 16 * c + 8 * ((d >> 2) & 1)) =
+          make_uint2(pk2bf(o[db][e] * inv, o[db][e + 1] * inv), pk2bf(o[db][e + 2] * inv, o[db][e + 3] * inv));
     }
-    return;
-  }
-  if (qi < q_len) {
-    bf16_t* op = a.out + (size_t)(q_off + qi) * a.out_stride + hq * D + 4 * h;
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the wave's own LDS writes, read back by itself
 #pragma unroll
-    for (int db = 0; db < 4; ++db)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const int e = 4 * b;
-        *reinterpret_cast<uint2*>(op + 32 * db + 8 * b) =
-            make_uint2(pk2bf(o[db][e] * inv, o[db][e + 1] * inv), pk2bf(o[db][e + 2] * inv, o[db][e + 3] * inv));
-      }
+  for (int i = 0; i < 8; ++i) {
+    const int r = 4 * i + (lane >> 4), c = lane & 15;
+    const u32x4 v = *reinterpret_cast<const u32x4*>(so + r * 256 + 16 * (c ^ (r & 15)));
+    if (pbase + r < q_len)
+      *reinterpret_cast<u32x4*>(a.out + (size_t)(q_off + pbase + r) * a.out_stride + hq * D + 8 * c) = v;
   }
 }
 
@@ -1459,43 +1340,29 @@ __global__ void attn_decode_reduce_kernel(DecodeArgs a, int D) {
 // Block order (prefill_block): a 1-D grid, head group fastest, so the heaviest causal tiles of every head
 // start first and consecutive blocks (round-robin over the XCDs) put one KV head on each XCD.
 // Kernel per config:
-//   * Llama (D 128, 4 query heads per KV head, causal, paged cache < 4 GiB): the software-pipelined
-//     8-wave kernel with the whole-row LDS epilogue (attn_prefill_v3_kernel<8, ..., WIDE>; 64-query
-//     tiles), tools/attn_pp_ab.py;
+//   * Llama (D 128, 4 query heads per KV head, causal, paged bf16 cache < 4 GiB): the software-pipelined
+//     8-wave kernel (attn_prefill_v3_kernel; 64-query tiles), tools/attn_pp_ab.py;
 //   * every other 4-heads-per-block config: attn_prefill_kernel with 8 waves (64-query tiles, two 32-row
 //     groups sharing each K/V tile);
 //   * 1 or 2 heads per block (encoders, GPT-2, odd GQA ratios): the 4-wave attn_prefill_kernel.
-template <int D, int GB, bool CAUSAL, bool PAGED>
+// F8 (fp8 cache: causal, paged, D 128): the generic kernel with the same block shapes, so the host's tile
+// list (ragk_attn_prefill_qtile) is the same for both cache formats.
+template <int D, int GB, bool CAUSAL, bool PAGED, bool F8 = false>
 hipError_t launch_prefill(PrefillArgs a, int n_tiles, hipStream_t st) {
   const int G = a.Hq / a.Hkv;
   const int n_hg = a.Hkv * (G / GB);
   a.n_hg = n_hg;
   const dim3 grid(n_tiles * n_hg);
-  if constexpr (D == 128 && GB == 4 && CAUSAL && PAGED) {
+  if constexpr (D == 128 && GB == 4 && CAUSAL && PAGED && !F8) {
     if (a.kv_bytes) {
-      hipLaunchKernelGGL((attn_prefill_v3_kernel<8, false, 0, 1, true>), grid, dim3(512), 0, st, a);
+      hipLaunchKernelGGL(attn_prefill_v3_kernel, grid, dim3(512), 0, st, a);
       return hipGetLastError();
     }
   }
   if constexpr (GB == 4)
-    hipLaunchKernelGGL((attn_prefill_kernel<D, GB, CAUSAL, PAGED, false, 8>), grid, dim3(512), 0, st, a);
+    hipLaunchKernelGGL((attn_prefill_kernel<D, GB, CAUSAL, PAGED, 8, F8>), grid, dim3(512), 0, st, a);
   else
-    hipLaunchKernelGGL((attn_prefill_kernel<D, GB, CAUSAL, PAGED>), grid, dim3(256), 0, st, a);
-  return hipGetLastError();
-}
-
-// fp8 cache: the generic kernel (causal, paged, D 128) with the block shapes of launch_prefill, so the host's
-// tile list (ragk_attn_prefill_qtile) is the same for both cache formats.
-template <int GB>
-hipError_t launch_prefill_fp8(PrefillArgs a, int n_tiles, hipStream_t st) {
-  const int G = a.Hq / a.Hkv;
-  const int n_hg = a.Hkv * (G / GB);
-  a.n_hg = n_hg;
-  const dim3 grid(n_tiles * n_hg);
-  if constexpr (GB == 4)
-    hipLaunchKernelGGL((attn_prefill_kernel<128, GB, true, true, false, 8, 0, false, true>), grid, dim3(512), 0, st, a);
-  else
-    hipLaunchKernelGGL((attn_prefill_kernel<128, GB, true, true, false, 4, 0, false, true>), grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL((attn_prefill_kernel<D, GB, CAUSAL, PAGED, 4, F8>), grid, dim3(256), 0, st, a);
   return hipGetLastError();
 }
 
@@ -1508,19 +1375,28 @@ RAGK_API int ragk_attn_prefill_qtile(int Hq, int Hkv) {
   return 32 * ((GB == 4 ? 8 : 4) / GB);
 }
 
-RAGK_API int ragk_attn_prefill(const void* q, int q_stride, const void* k, const void* v, int kv_stride,
-                               const int* block_tables, int bt_stride, const int* cu_q, const int* cu_kv,
-                               const int* kv_lens, const int* tiles, int n_tiles, void* out, int out_stride,
-                               int Hq, int Hkv, int D, int causal, int paged, float scale, hipStream_t st) {
+// ks / vs non-null: fp8 cache (kv_fp8.h): k / v [nblocks][Hkv][64][128] e4m3 bytes, ks / vs [nblocks][Hkv][64]
+// fp32 row scales; causal paged attention at D = 128 only.
+RAGK_API int ragk_attn_prefill(const void* q, int q_stride, const void* k, const void* v, const float* ks,
+                               const float* vs, int kv_stride, const int* block_tables, int bt_stride,
+                               const int* cu_q, const int* cu_kv, const int* kv_lens, const int* tiles, int n_tiles,
+                               void* out, int out_stride, int Hq, int Hkv, int D, int causal, int paged, float scale,
+                               hipStream_t st) {
   if (n_tiles <= 0) return 0;
-  if (Hq % Hkv) return (int)hipErrorInvalidValue;
-  // paged: kv_stride = number of cache blocks (sizes the buffer descriptors of the BUF staging)
-  const unsigned long long cache_bytes = paged ? (unsigned long long)kv_stride * Hkv * KT * D * 2 : 0ull;
+  if (Hq % Hkv || (ks != nullptr) != (vs != nullptr)) return (int)hipErrorInvalidValue;
+  if (ks && (D != 128 || !paged || !causal || !k || !v || !block_tables)) return (int)hipErrorInvalidValue;
+  // paged bf16 cache: kv_stride = number of cache blocks (sizes the pipelined kernel's buffer descriptors)
+  const unsigned long long cache_bytes = paged && !ks ? (unsigned long long)kv_stride * Hkv * KT * D * 2 : 0ull;
   PrefillArgs a{(const bf16_t*)q, q_stride, (const bf16_t*)k, (const bf16_t*)v, kv_stride, block_tables, bt_stride,
                 cu_q, cu_kv, kv_lens, tiles, (bf16_t*)out, out_stride, Hq, Hkv, scale * 1.4426950408889634f,
-                cache_bytes < (1ull << 32) ? (unsigned)cache_bytes : 0u, 0};
+                cache_bytes < (1ull << 32) ? (unsigned)cache_bytes : 0u, 0, ks, vs};
   const int G = Hq / Hkv;
   const int GB = G % 4 == 0 ? 4 : (G % 2 == 0 ? 2 : 1);
+  if (ks) {
+    if (GB == 4) return (int)launch_prefill<128, 4, true, true, true>(a, n_tiles, st);
+    if (GB == 2) return (int)launch_prefill<128, 2, true, true, true>(a, n_tiles, st);
+    return (int)launch_prefill<128, 1, true, true, true>(a, n_tiles, st);
+  }
 #define RAGK_PF(DD, GG, CC, PP)                                                          \
   if (D == DD && GB == GG && (bool)causal == CC && (bool)paged == PP)                      \
     return (int)launch_prefill<DD, GG, CC, PP>(a, n_tiles, st);
@@ -1538,83 +1414,26 @@ RAGK_API int ragk_attn_prefill(const void* q, int q_stride, const void* k, const
   return (int)hipErrorInvalidValue;
 }
 
-
-// K/V cache-policy switch for decode (0 = default, 1 = non-temporal loads; the KV stream is read
-// once per step). A/B in tools/bench_kernels.py --quick.
-static int g_decode_nt = 0;
-// 8-wave single-partition decode attention once batch x KV heads reaches this (0 = never)
-static int g_decode_nw8_min = 0;
-// diagnostic instantiation of the 8-wave kernel (DG above; A/B tooling only, 0 = off)
-static int g_decode_diag = 0;
-// single-partition grid on 4-wave blocks with K tiles by LDS-DMA (KL above; 0 = the 8-wave kernel)
-static int g_decode_kl = 0;
-RAGK_API int ragk_attn_decode_set_kl(int on) {
-  g_decode_kl = on ? 1 : 0;
-  return 0;
-}
-RAGK_API int ragk_attn_decode_set_diag(int dg) {
-  g_decode_diag = (dg == 1 || dg == 2) ? dg : 0;
-  return 0;
-}
-RAGK_API int ragk_attn_decode_set_nw8(int min_pairs) {
-  g_decode_nw8_min = min_pairs > 0 ? min_pairs : 0;
-  return 0;
-}
-RAGK_API int ragk_attn_decode_set_nt(int nt) {
-  g_decode_nt = nt ? 1 : 0;
-  return 0;
-}
-
-static int launch_attn_decode(DecodeArgs a, int B, int D, int max_parts, hipStream_t st);
-
-// Deferred merge: the next decode-attention launches leave the split-K partitions unmerged (no
-// attn_decode_reduce launch) for a consumer that merges them itself (gemm_part.hip MergeArgs: the
-// o_proj GEMM). The host sets it around one launch.
-static int g_decode_defer = 0;
-RAGK_API int ragk_attn_decode_set_defer(int on) {
-  g_decode_defer = on ? 1 : 0;
-  return 0;
-}
-
-RAGK_API int ragk_attn_decode(const void* q, int q_stride, const void* kc, const void* vc, const int* block_tables,
-                              int bt_stride, const int* kv_lens, float* part_o, float* part_ml, void* out,
-                              int out_stride, int B, int Hq, int Hkv, int D, int part_tiles, int max_parts,
-                              float scale, hipStream_t st) {
-  if (B <= 0) return 0;
-  if (Hq % Hkv || part_tiles < 1 || max_parts < 1 || max_parts > RED_MAXP) return (int)hipErrorInvalidValue;
-  DecodeArgs a{(const bf16_t*)q, q_stride, (const bf16_t*)kc, (const bf16_t*)vc, block_tables, bt_stride, kv_lens,
-               part_o, part_ml, (bf16_t*)out, out_stride, Hq, Hkv, part_tiles, max_parts,
-               scale * 1.4426950408889634f};
-  return launch_attn_decode(a, B, D, max_parts, st);
-}
-
-// Decode attention fed by the qkv projection's split-K partial slabs P[S][B][ldp] (gemm_part.hip):
-// RoPE of q and k, the KV append at slots[b] and the attention in one launch (replaces
-// rope_kv_partials + attn_decode). Cache blocks hold KT tokens.
-RAGK_API int ragk_attn_decode_rope(const float* P, int S, int ldp, const int* positions, const int* slots,
-                                   const float* cos_t, const float* sin_t, void* kc, void* vc,
-                                   const int* block_tables, int bt_stride, const int* kv_lens, float* part_o,
-                                   float* part_ml, void* out, int out_stride, int B, int Hq, int Hkv, int D,
-                                   int part_tiles, int max_parts, float scale, hipStream_t st) {
-  if (B <= 0) return 0;
-  if (Hq % Hkv || part_tiles < 1 || max_parts < 1 || max_parts > RED_MAXP || S < 1 || D % 64 ||
-      ldp < (Hq + 2 * Hkv) * D || !P || !positions || !slots || !cos_t || !sin_t)
-    return (int)hipErrorInvalidValue;
-  DecodeArgs a{nullptr, 0, (const bf16_t*)kc, (const bf16_t*)vc, block_tables, bt_stride, kv_lens,
-               part_o, part_ml, (bf16_t*)out, out_stride, Hq, Hkv, part_tiles, max_parts,
-               scale * 1.4426950408889634f, P, (long long)B * ldp, ldp, S, positions, slots, cos_t, sin_t};
-  return launch_attn_decode(a, B, D, max_parts, st);
-}
+// Launch policy of one decode-attention call (`flags` of ragk_attn_decode; mirrored in ops/native.py).
+enum : unsigned {
+  DEC_NT = 1u << 0,           // non-temporal K / V loads (the KV stream is read once per step)
+  DEC_SINGLE = 1u << 1,       // the host sized this batch for the single-partition grid (max_parts == 1)
+  DEC_KL = 1u << 2,           // single-partition grid: 4-wave blocks with K tiles by LDS-DMA (KL above)
+  DEC_DEFER_MERGE = 1u << 3,  // no attn_decode_reduce launch: the consumer merges the partitions itself
+                              // (gemm_part.hip MergeArgs: the o_proj GEMM)
+  DEC_DIAG_SHIFT = 4,         // bits 4-5: DG instantiation of the 8-wave kernel (tools/attn_decode_probe.py)
+  DEC_ALL = 0x3fu,
+};
 
 // fp8 cache (a.ks set): the same routes as the bf16 D = 128 dispatch below -- the single-partition grid on
 // KL-style 4-wave blocks (K tiles by LDS-DMA), else split-K 4-wave blocks + reduce; nt loads on and off.
-static int launch_attn_decode_fp8(DecodeArgs a, int B, int D, int max_parts, hipStream_t st) {
+static int launch_attn_decode_fp8(DecodeArgs a, int B, int D, int max_parts, unsigned flags, hipStream_t st) {
   const int Hq = a.Hq, Hkv = a.Hkv;
   const int G = Hq / Hkv;
-  if (D != 128 || !a.vs) return (int)hipErrorInvalidValue;
+  if (D != 128) return (int)hipErrorInvalidValue;
   dim3 grid(max_parts, Hkv, B);
-  if (G == 4 && max_parts == 1 && g_decode_kl && g_decode_nw8_min > 0 && B * Hkv >= g_decode_nw8_min) {
-    if (g_decode_nt)
+  if (G == 4 && max_parts == 1 && (flags & DEC_KL) && (flags & DEC_SINGLE)) {
+    if (flags & DEC_NT)
       hipLaunchKernelGGL((attn_decode_kernel<128, 4, true, 4, 0, true, true>), grid, dim3(256), 0, st, a);
     else
       hipLaunchKernelGGL((attn_decode_kernel<128, 4, false, 4, 0, true, true>), grid, dim3(256), 0, st, a);
@@ -1622,11 +1441,11 @@ static int launch_attn_decode_fp8(DecodeArgs a, int B, int D, int max_parts, hip
   }
 #define RAGK_DC8(GG)                                                                               \
   if (G == GG) {                                                                                   \
-    if (g_decode_nt)                                                                               \
+    if (flags & DEC_NT)                                                                            \
       hipLaunchKernelGGL((attn_decode_kernel<128, GG, true, 4, 0, false, true>), grid, dim3(256), 0, st, a);  \
     else                                                                                           \
       hipLaunchKernelGGL((attn_decode_kernel<128, GG, false, 4, 0, false, true>), grid, dim3(256), 0, st, a); \
-    if (max_parts > 1 && !g_decode_defer)                                                          \
+    if (max_parts > 1 && !(flags & DEC_DEFER_MERGE))                                               \
       hipLaunchKernelGGL(attn_decode_reduce_kernel, dim3(Hq, B), dim3(128), 0, st, a, 128);        \
     return (int)hipGetLastError();                                                                 \
   }
@@ -1638,20 +1457,30 @@ static int launch_attn_decode_fp8(DecodeArgs a, int B, int D, int max_parts, hip
   return (int)hipErrorInvalidValue;
 }
 
-static int launch_attn_decode(DecodeArgs a, int B, int D, int max_parts, hipStream_t st) {
+// The kernel(s) of one call: a pure function of (a, B, D, max_parts, flags). What each flag stands for in
+// terms of the process-wide switches this dispatch used to read:
+//   DEC_NT            g_decode_nt
+//   DEC_SINGLE        g_decode_nw8_min > 0 && B * Hkv >= g_decode_nw8_min (the host compares now)
+//   DEC_KL            g_decode_kl
+//   DEC_DEFER_MERGE   g_decode_defer
+//   DIAG bits (0-2)   g_decode_diag
+// The structural conditions of the single-partition grid stay here: D == 128, G == 4, max_parts == 1 (fp8:
+// and DEC_KL, there is no 8-wave fp8 kernel).
+static int launch_attn_decode(DecodeArgs a, int B, int D, int max_parts, unsigned flags, hipStream_t st) {
   const int Hq = a.Hq, Hkv = a.Hkv;
   const int G = Hq / Hkv;
-  if (a.ks) return launch_attn_decode_fp8(a, B, D, max_parts, st);
+  const unsigned diag = (flags >> DEC_DIAG_SHIFT) & 3u;
+  if (a.ks) return launch_attn_decode_fp8(a, B, D, max_parts, flags, st);
   dim3 grid(max_parts, Hkv, B);
-  if (D == 128 && G == 4 && max_parts == 1 && g_decode_nw8_min > 0 && B * Hkv >= g_decode_nw8_min) {
+  if (D == 128 && G == 4 && max_parts == 1 && (flags & DEC_SINGLE)) {
     // one partition per sequence over >= 1 block per CU: 8-wave blocks, no merge launch
-    if (g_decode_kl && !g_decode_diag)
+    if ((flags & DEC_KL) && !diag)
       hipLaunchKernelGGL((attn_decode_kernel<128, 4, true, 4, 0, true>), grid, dim3(256), 0, st, a);
-    else if (g_decode_diag == 1)
+    else if (diag == 1)
       hipLaunchKernelGGL((attn_decode_kernel<128, 4, true, 8, 1>), grid, dim3(512), 0, st, a);
-    else if (g_decode_diag == 2)
+    else if (diag == 2)
       hipLaunchKernelGGL((attn_decode_kernel<128, 4, true, 8, 2>), grid, dim3(512), 0, st, a);
-    else if (g_decode_nt)
+    else if (flags & DEC_NT)
       hipLaunchKernelGGL((attn_decode_kernel<128, 4, true, 8>), grid, dim3(512), 0, st, a);
     else
       hipLaunchKernelGGL((attn_decode_kernel<128, 4, false, 8>), grid, dim3(512), 0, st, a);
@@ -1659,11 +1488,11 @@ static int launch_attn_decode(DecodeArgs a, int B, int D, int max_parts, hipStre
   }
 #define RAGK_DC(DD, GG)                                                            \
   if (D == DD && G == GG) {                                                          \
-    if (g_decode_nt)                                                                 \
+    if (flags & DEC_NT)                                                              \
       hipLaunchKernelGGL((attn_decode_kernel<DD, GG, true>), grid, dim3(256), 0, st, a); \
     else                                                                             \
       hipLaunchKernelGGL((attn_decode_kernel<DD, GG, false>), grid, dim3(256), 0, st, a); \
-    if (max_parts > 1 && !g_decode_defer)                                            \
+    if (max_parts > 1 && !(flags & DEC_DEFER_MERGE))                                 \
       hipLaunchKernelGGL(attn_decode_reduce_kernel, dim3(Hq, B), dim3(DD), 0, st, a, DD); \
     return (int)hipGetLastError();                                                   \
   }
@@ -1677,48 +1506,32 @@ static int launch_attn_decode(DecodeArgs a, int B, int D, int max_parts, hipStre
   return (int)hipErrorInvalidValue;
 }
 
-
-// ---- fp8 KV cache entry points (kv_fp8.h): k8 / v8 [nblocks][Hkv][64][128] e4m3 bytes, ks / vs [nblocks][Hkv][64]
-// fp32 row scales. Same arguments as the bf16 forms plus the two scale arrays; D must be 128.
-RAGK_API int ragk_attn_prefill_fp8(const void* q, int q_stride, const void* k8, const void* v8, const float* ks,
-                                   const float* vs, const int* block_tables, int bt_stride, const int* cu_q,
-                                   const int* kv_lens, const int* tiles, int n_tiles, void* out, int out_stride,
-                                   int Hq, int Hkv, int D, float scale, hipStream_t st) {
-  if (n_tiles <= 0) return 0;
-  if (Hq % Hkv || D != 128 || !k8 || !v8 || !ks || !vs || !block_tables) return (int)hipErrorInvalidValue;
-  PrefillArgs a{(const bf16_t*)q, q_stride, (const bf16_t*)k8, (const bf16_t*)v8, 0, block_tables, bt_stride,
-                cu_q, nullptr, kv_lens, tiles, (bf16_t*)out, out_stride, Hq, Hkv, scale * 1.4426950408889634f,
-                0u, 0, ks, vs};
-  const int G = Hq / Hkv;
-  if (G % 4 == 0) return (int)launch_prefill_fp8<4>(a, n_tiles, st);
-  if (G % 2 == 0) return (int)launch_prefill_fp8<2>(a, n_tiles, st);
-  return (int)launch_prefill_fp8<1>(a, n_tiles, st);
-}
-
-RAGK_API int ragk_attn_decode_fp8(const void* q, int q_stride, const void* k8, const void* v8, const float* ks,
-                                  const float* vs, const int* block_tables, int bt_stride, const int* kv_lens,
-                                  float* part_o, float* part_ml, void* out, int out_stride, int B, int Hq, int Hkv,
-                                  int D, int part_tiles, int max_parts, float scale, hipStream_t st) {
+// Decode attention over the paged cache (blocks of KT tokens). The query is given one of two ways:
+//   * q / q_stride: bf16 rows; the cache already holds the new token;
+//   * P, S, ldp, positions, slots, cos_t, sin_t: the qkv projection's split-K partial slabs P[S][B][ldp]
+//     (gemm_part.hip): RoPE of q and k, the KV append at slots[b] and the attention in one launch (replaces
+//     rope_kv_partials + attn_decode).
+// ks / vs non-null: fp8 cache (kv_fp8.h): kc / vc [nblocks][Hkv][64][128] e4m3 bytes, ks / vs [nblocks][Hkv][64]
+// fp32 row scales; D must be 128. flags: the DEC_* launch policy above.
+RAGK_API int ragk_attn_decode(const void* q, int q_stride, const float* P, int S, int ldp, const int* positions,
+                              const int* slots, const float* cos_t, const float* sin_t, void* kc, void* vc,
+                              float* ks, float* vs, const int* block_tables, int bt_stride, const int* kv_lens,
+                              float* part_o, float* part_ml, void* out, int out_stride, int B, int Hq, int Hkv,
+                              int D, int part_tiles, int max_parts, float scale, unsigned flags, hipStream_t st) {
   if (B <= 0) return 0;
-  if (Hq % Hkv || part_tiles < 1 || max_parts < 1 || max_parts > RED_MAXP || !ks || !vs)
+  if (Hq % Hkv || part_tiles < 1 || max_parts < 1 || max_parts > RED_MAXP || (q != nullptr) == (P != nullptr) ||
+      (ks != nullptr) != (vs != nullptr) ||
+      (flags & ~DEC_ALL) || ((flags >> DEC_DIAG_SHIFT) & 3u) == 3u || (ks && D != 128))
     return (int)hipErrorInvalidValue;
-  DecodeArgs a{(const bf16_t*)q, q_stride, (const bf16_t*)k8, (const bf16_t*)v8, block_tables, bt_stride, kv_lens,
-               part_o, part_ml, (bf16_t*)out, out_stride, Hq, Hkv, part_tiles, max_parts,
-               scale * 1.4426950408889634f, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, ks, vs};
-  return launch_attn_decode(a, B, D, max_parts, st);
-}
-
-RAGK_API int ragk_attn_decode_rope_fp8(const float* P, int S, int ldp, const int* positions, const int* slots,
-                                       const float* cos_t, const float* sin_t, void* k8, void* v8, float* ks,
-                                       float* vs, const int* block_tables, int bt_stride, const int* kv_lens,
-                                       float* part_o, float* part_ml, void* out, int out_stride, int B, int Hq,
-                                       int Hkv, int D, int part_tiles, int max_parts, float scale, hipStream_t st) {
-  if (B <= 0) return 0;
-  if (Hq % Hkv || part_tiles < 1 || max_parts < 1 || max_parts > RED_MAXP || S < 1 || D != 128 ||
-      ldp < (Hq + 2 * Hkv) * D || !P || !positions || !slots || !cos_t || !sin_t || !ks || !vs)
+  if (P && (S < 1 || D % 64 || ldp < (Hq + 2 * Hkv) * D || !positions || !slots || !cos_t || !sin_t))
     return (int)hipErrorInvalidValue;
-  DecodeArgs a{nullptr, 0, (const bf16_t*)k8, (const bf16_t*)v8, block_tables, bt_stride, kv_lens,
+  DecodeArgs a{(const bf16_t*)q, q_stride, (const bf16_t*)kc, (const bf16_t*)vc, block_tables, bt_stride, kv_lens,
                part_o, part_ml, (bf16_t*)out, out_stride, Hq, Hkv, part_tiles, max_parts,
-               scale * 1.4426950408889634f, P, (long long)B * ldp, ldp, S, positions, slots, cos_t, sin_t, ks, vs};
-  return launch_attn_decode(a, B, D, max_parts, st);
+               scale * 1.4426950408889634f};
+  if (P) {
+    a.qkv_p = P, a.p_slab = (long long)B * ldp, a.ldp = ldp, a.S = S;
+    a.positions = positions, a.slots = slots, a.cos_t = cos_t, a.sin_t = sin_t;
+  }
+  a.ks = ks, a.vs = vs;
+  return launch_attn_decode(a, B, D, max_parts, flags, st);
 }

@@ -446,15 +446,9 @@ int launch_part_mt(const void* X, int ldx, const void* W, int ldw, float* P, int
 // Slice choice: K-slice KS = 64 * ks_steps (ks_steps in {4, 8, 14, 16, 28, 32}; 14 / 28 divide the
 // K = 14336 of Llama's down projection into 16 / 8 slabs; 4 = 256-wide slices for the narrow K of
 // tensor-parallel shards: down at TP=8 has K = 1792 = 7 x 256, o_proj K = 512); S = K / KS slabs.
-// Picks the largest slice that still gives >= g_part_min_blocks blocks and fits the activation slice
+// Picks the largest slice that still gives >= min_blocks blocks and fits the activation slice
 // in LDS, else the smallest legal slice (most blocks).
-static int g_part_min_blocks = 256;
-RAGK_API int ragk_gemm_part_set_min_blocks(int n) {
-  g_part_min_blocks = n > 0 ? n : 256;
-  return 0;
-}
-
-RAGK_API int ragk_gemm_part_ksteps(int M, int N, int K) {
+RAGK_API int ragk_gemm_part_ksteps(int M, int N, int K, int min_blocks) {
   const int mt = (M + 15) / 16;
   const int nb = (N + PT_NB - 1) / PT_NB;
   int best = 0;
@@ -463,7 +457,7 @@ RAGK_API int ragk_gemm_part_ksteps(int M, int N, int K) {
     if (K % KS) continue;
     if (16 * mt * KS * 2 > 128 * 1024 || (16 * mt * KS * 2) % 8192) continue;  // LDS; 8 waves x 1-KiB DMA pieces
     if (best == 0) best = ks;  // largest legal slice
-    if (nb * (K / KS) >= g_part_min_blocks) return ks;
+    if (nb * (K / KS) >= min_blocks) return ks;
     best = ks;
   }
   return best;
@@ -537,7 +531,7 @@ RAGK_API int ragk_gemm_part_fp8(const void* X, int ldx, const void* W8, int ldw,
 }
 
 // o_proj fed by the decode attention's unmerged partitions (MG above; the attention launched with its
-// merge deferred, ragk_attn_decode_set_defer). X (bf16 rows, out_stride) is the attention output buffer:
+// merge deferred, ragk_attn_decode's DEC_DEFER_MERGE flag). X (bf16 rows, out_stride) is the attention output buffer:
 // rows whose sequence used one partition are read from it. M <= 4, head dim 128, K = Hq * 128, 8- or
 // 4-step K-slices (a 16-step slice spills), at most MG_MAXPP partitions per thread. w8 / wscale: fp8 weights (ldw in bytes).
 RAGK_API int ragk_gemm_part_merge(const float* part_o, const float* part_ml, const void* out, int out_stride,

@@ -343,8 +343,8 @@ __global__ __launch_bounds__(ST_THREADS, ROWS == 64 ? 2 : 1) void gemm_stream_ke
   if (tid == 0) __hip_atomic_store(counters + ntile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Weight-stream cache policy for the SiLU*up (gate/up) instantiations: 1 = non-temporal.
-int g_stream_nt = 1;
+// Weight-stream cache policy for the SiLU*up (gate/up) instantiations: non-temporal.
+constexpr bool g_stream_nt = true;
 // diagnostic build of the SiLU*up 64-row kernel (DG above; A/B tooling only)
 int g_stream_diag = 0;
 // Tile rows for the SiLU*up GEMM: 64 = two blocks per CU over 64-row (32 gate + 32 up) tiles, so the
@@ -426,11 +426,6 @@ int dispatch_stream(const void* X, int ldx, const void* W, int ldw, const float*
 // 8 K-steps per block, S | K-steps.
 RAGK_API int ragk_gemm_stream_set_diag(int dg) {
   g_stream_diag = (dg >= 1 && dg <= 3) ? dg : 0;
-  return 0;
-}
-
-RAGK_API int ragk_gemm_stream_set_nt(int nt) {
-  g_stream_nt = nt ? 1 : 0;
   return 0;
 }
 

@@ -24,7 +24,6 @@ _SIGS = {
     "ragk_gemm_path": [I, P, I, P, I, P, I, P, P, I, I, I, I, I, S],
     "ragk_gemm_pp": [P, I, P, I, P, I, P, P, I, I, I, I, I, I, S],
     "ragk_gemm_w4_set_grid": [I],
-    "ragk_gemm_stream_set_nt": [I],
     "ragk_gemm_stream_set_diag": [I],
     "ragk_gemm_stream_set_pair_rows": [I],
     "ragk_gemm_w4": [P, I, P, I, P, I, P, P, I, I, I, I, I, I, P, I, S],
@@ -33,11 +32,6 @@ _SIGS = {
     "ragk_gemm_part": [P, I, P, I, P, I, I, I, I, S],
     "ragk_gemm_part_norm": [P, I, P, F, P, I, P, I, I, I, I, S],
     "ragk_gemm_part_fp8": [P, I, P, I, P, P, I, I, I, I, S],
-    "ragk_attn_decode_set_nt": [I],
-    "ragk_attn_decode_set_nw8": [I],
-    "ragk_attn_decode_set_defer": [I],
-    "ragk_attn_decode_set_diag": [I],
-    "ragk_attn_decode_set_kl": [I],
     "ragk_gemm_part_merge": [P, P, P, I, P, I, I, I, P, I, P, P, I, I, I, I, S],
     "ragk_gemm_part_merge_ok": [I, I, I, I, I],
     "ragk_gemm_stream_part": [P, I, P, I, P, I, I, I, I, I, S],
@@ -53,8 +47,7 @@ _SIGS = {
     "ragk_host_word_free": [P],
     "ragk_mlp_engine_ctr_bytes": [],
     "ragk_mlp_engine_split": [I, I, I, I, P],
-    "ragk_gemm_part_ksteps": [I, I, I],
-    "ragk_gemm_part_set_min_blocks": [I],
+    "ragk_gemm_part_ksteps": [I, I, I, I],
     "ragk_add_partials_rmsnorm": [P, I, I, P, I, P, P, I, I, F, S],
     "ragk_rope_kv_partials": [P, I, I, I, P, I, P, P, P, P, P, P, I, I, I, I, S],
     "ragk_gemm_dec": [P, I, P, I, P, I, P, P, I, I, I, I, I, I, I, P, P, S],
@@ -73,15 +66,13 @@ _SIGS = {
     "ragk_silu_mul": [P, I, P, I, I, I, S],
     "ragk_gather_rows": [P, I, P, P, I, I, I, S],
     "ragk_attn_prefill_qtile": [I, I],
-    "ragk_attn_prefill": [P, I, P, P, I, P, I, P, P, P, P, I, P, I, I, I, I, I, I, F, S],
-    "ragk_attn_decode": [P, I, P, P, P, I, P, P, P, P, I, I, I, I, I, I, I, F, S],
-    "ragk_attn_decode_rope": [P, I, I, P, P, P, P, P, P, P, I, P, P, P, P, I, I, I, I, I, I, I, F, S],
+    # null k / v scale pointers = bf16 cache; ragk_attn_decode: q or the qkv partial slabs, flags last
+    "ragk_attn_prefill": [P, I, P, P, P, P, I, P, I, P, P, P, P, I, P, I, I, I, I, I, I, F, S],
+    "ragk_attn_decode": [P, I, P, I, I, P, P, P, P, P, P, P, P, P, I, P, P, P, P, I, I, I, I, I, I, I, F,
+                         ctypes.c_uint, S],
     # fp8 KV cache forms (kv_fp8.h): the bf16 signatures plus the k / v row-scale arrays
     "ragk_rope_kv_fp8": [P, I, P, P, P, P, P, P, P, P, I, I, I, I, I, S],
     "ragk_rope_kv_partials_fp8": [P, I, I, I, P, I, P, P, P, P, P, P, P, P, I, I, I, I, S],
-    "ragk_attn_prefill_fp8": [P, I, P, P, P, P, P, I, P, P, P, I, P, I, I, I, I, F, S],
-    "ragk_attn_decode_fp8": [P, I, P, P, P, P, P, I, P, P, P, P, I, I, I, I, I, I, I, F, S],
-    "ragk_attn_decode_rope_fp8": [P, I, I, P, P, P, P, P, P, P, P, P, I, P, P, P, P, I, I, I, I, I, I, I, F, S],
     "ragk_topk_candidates": [P, I, I, I, I, I, I, P, P, S],
     "ragk_sample_candidates": [P, P, I, I, P, P, P, P, P, P, P, S],
     "ragk_sample_candidates_lists": [P, P, I, I, I, P, P, P, P, P, P, P, S],

@@ -299,15 +299,11 @@ def gemm(x, w, bias=None, resid=None, epi="none", out=None, out_f32=False, path=
 
 
 PART_MIN_BLOCKS = 512
-_part_cfg = [False]
 
 
 def gemm_part_slabs(M, N, K, ks=None):
     """(ks_steps, S) of the split-K partial GEMM for this shape (0, 0 if unsupported)."""
-    if not _part_cfg[0]:
-        check(_lib.lib().ragk_gemm_part_set_min_blocks(PART_MIN_BLOCKS), "ragk_gemm_part_set_min_blocks")
-        _part_cfg[0] = True
-    ks = ks or _lib.lib().ragk_gemm_part_ksteps(M, N, K)
+    ks = ks or _lib.lib().ragk_gemm_part_ksteps(M, N, K, PART_MIN_BLOCKS)
     if ks <= 0 or K % (64 * ks):
         return 0, 0
     return ks, K // (64 * ks)
@@ -1191,42 +1187,38 @@ def build_last_rows_lists(q_lens, rows, Hq, Hkv, tiles=None):
 
 def attn_prefill(q, k, v, cu_q, kv_lens, tiles, out, Hq, Hkv, D, causal=True, paged=True, block_tables=None,
                  cu_kv=None, kv_stride=0, scale=None):
-    """q: [T, >=Hq*D] bf16 (row stride arbitrary). paged: k/v caches [nb, Hkv, 64, D];
+    """q: [T, >=Hq*D] bf16 (row stride arbitrary). paged: k/v caches [nb, Hkv, 64, D] (bf16 or Fp8KV);
     else packed k/v row pointers with `kv_stride` (element stride per token)."""
     _req(q.dtype == torch.bfloat16 and q.stride(-1) == 1, "q")
     _req(tiles.dtype == torch.int32 and tiles.is_cuda and tiles.is_contiguous(), "tiles int32 on GPU")
     _req(D in (32, 64, 128), "head_dim must be 32/64/128")
-    if isinstance(k, Fp8KV) or isinstance(v, Fp8KV):
+    f8 = isinstance(k, Fp8KV) or isinstance(v, Fp8KV)
+    if f8:
         _req(paged and causal, "fp8 KV cache: paged causal attention only")
         _kv8(k, v, Hkv, D, q.device)
-        _req(block_tables is not None and block_tables.dtype == torch.int32, "block_tables int32")
-        _req(block_tables.stride(0) <= 2048, "prefill block tables wider than 2048 blocks (128k tokens)")
-        scale = 1.0 / math.sqrt(D) if scale is None else scale
-        check(_lib.lib().ragk_attn_prefill_fp8(
-            q.data_ptr(), q.stride(0), k.data.data_ptr(), v.data.data_ptr(), k.scale.data_ptr(), v.scale.data_ptr(),
-            block_tables.data_ptr(), block_tables.stride(0), cu_q.data_ptr(), kv_lens.data_ptr(), tiles.data_ptr(),
-            tiles.shape[0], out.data_ptr(), out.stride(0), Hq, Hkv, D, float(scale), stream_ptr()),
-            "ragk_attn_prefill_fp8")
-        return out
     if paged:
-        _req(k.dim() == 4 and k.shape[2] == 64 and k.shape[1] == Hkv and k.shape[3] == D, "paged cache [nb,Hkv,64,D]")
-        _req(block_tables is not None and block_tables.dtype == torch.int32, "block_tables int32")
-        _req(block_tables.stride(0) <= 2048, "prefill block tables wider than 2048 blocks (128k tokens)")
-    scale = 1.0 / math.sqrt(D) if scale is None else scale
-    n_tiles = tiles.shape[0]
-    if paged:
+        _req(len(k.shape) == 4 and k.shape[2] == 64 and k.shape[1] == Hkv and k.shape[3] == D, "paged cache [nb,Hkv,64,D]")
         _req(v.shape == k.shape, "paged k/v caches differ in shape")
-        kv_stride = k.shape[0]  # paged: the cache block count (sizes the kernel's buffer descriptors)
+        _req(block_tables is not None and block_tables.dtype == torch.int32, "block_tables int32")
+        _req(block_tables.stride(0) <= 2048, "prefill block tables wider than 2048 blocks (128k tokens)")
+        kv_stride = k.shape[0]  # the cache block count (sizes the pipelined kernel's buffer descriptors)
+    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    kd, vd, ks, vs = (k.data, v.data, k.scale, v.scale) if f8 else (k, v, None, None)
     check(_lib.lib().ragk_attn_prefill(
-        q.data_ptr(), q.stride(0), k.data_ptr(), v.data_ptr(), kv_stride, ptr(block_tables),
+        q.data_ptr(), q.stride(0), kd.data_ptr(), vd.data_ptr(), ptr(ks), ptr(vs), kv_stride, ptr(block_tables),
         block_tables.stride(0) if block_tables is not None else 0, cu_q.data_ptr(), ptr(cu_kv), kv_lens.data_ptr(),
-        tiles.data_ptr(), n_tiles, out.data_ptr(), out.stride(0), Hq, Hkv, D, int(causal), int(paged), float(scale),
-        stream_ptr()), "ragk_attn_prefill")
+        tiles.data_ptr(), tiles.shape[0], out.data_ptr(), out.stride(0), Hq, Hkv, D, int(causal), int(paged),
+        float(scale), stream_ptr()), "ragk_attn_prefill")
     return out
 
 
 DECODE_TARGET_BLOCKS = 512
 DECODE_MIN_TILES = 4
+
+
+def _decode_single(batch, Hkv):
+    """Whether this batch takes the single-partition decode grid (DECODE_NW8_MIN_PAIRS below)."""
+    return DECODE_NW8_MIN_PAIRS > 0 and batch * Hkv >= DECODE_NW8_MIN_PAIRS
 
 
 def decode_partitions(max_kv_len, batch, Hkv, target_blocks=None, min_tiles=None):
@@ -1238,7 +1230,7 @@ def decode_partitions(max_kv_len, batch, Hkv, target_blocks=None, min_tiles=None
     target_blocks = DECODE_TARGET_BLOCKS if target_blocks is None else target_blocks
     min_tiles = DECODE_MIN_TILES if min_tiles is None else min_tiles
     max_kt = max(1, (max_kv_len + 63) // 64)
-    if DECODE_NW8_MIN_PAIRS > 0 and batch * Hkv >= DECODE_NW8_MIN_PAIRS:
+    if _decode_single(batch, Hkv):
         return min_tiles, 1  # one 8-wave block per (sequence, KV head), no merge (attention.hip NW = 8)
     mp = max(1, min(-(-target_blocks // (batch * Hkv)), -(-max_kt // min_tiles)))
     return min_tiles, mp
@@ -1265,44 +1257,58 @@ DECODE_NT_MIN_BH = 64
 # tools/attn_decode_probe.py, profiles/attn_decode_probe_r6.log.
 DECODE_KL = os.environ.get("RAGK_DECODE_KL", "1") != "0"
 
+# Diagnostic instantiation of the 8-wave kernel (attention.hip DG: 1 / 2); set by tools/attn_decode_probe.py only.
+DECODE_DIAG = 0
 
-def _set_decode_nt(B, Hkv):
-    L = _lib.lib()
-    check(L.ragk_attn_decode_set_nt(1 if B * Hkv >= DECODE_NT_MIN_BH else 0), "ragk_attn_decode_set_nt")
-    check(L.ragk_attn_decode_set_nw8(DECODE_NW8_MIN_PAIRS), "ragk_attn_decode_set_nw8")
-    check(L.ragk_attn_decode_set_kl(1 if DECODE_KL else 0), "ragk_attn_decode_set_kl")
+# `flags` of ragk_attn_decode: the launch policy of one call (attention.hip DEC_*)
+DEC_NT, DEC_SINGLE, DEC_KL, DEC_DEFER_MERGE, DEC_DIAG_SHIFT = 1, 2, 4, 8, 4
+
+
+def decode_flags(B, Hkv, defer_merge=False):
+    """The policy word of one decode-attention launch, from the module constants as they are now."""
+    return ((DEC_NT if B * Hkv >= DECODE_NT_MIN_BH else 0) | (DEC_SINGLE if _decode_single(B, Hkv) else 0)
+            | (DEC_KL if DECODE_KL else 0) | (DEC_DEFER_MERGE if defer_merge else 0)
+            | (DECODE_DIAG << DEC_DIAG_SHIFT))
+
+
+def _launch_attn_decode(q, rope, k_cache, v_cache, block_tables, kv_lens, out, Hq, Hkv, D, part_tiles, max_parts, ws_o,
+                        ws_ml, scale, defer_merge=False):
+    """The checks, the partition workspace and the one launch shared by attn_decode (q rows, rope None) and
+    attn_decode_rope (q None; rope = (P, positions, slots, cos_t, sin_t))."""
+    B = kv_lens.numel()
+    dev = out.device
+    f8 = isinstance(k_cache, Fp8KV) or isinstance(v_cache, Fp8KV)
+    if f8:
+        _kv8(k_cache, v_cache, Hkv, D, dev)
+    _req(len(k_cache.shape) == 4 and k_cache.shape[1] == Hkv and k_cache.shape[2] == 64 and k_cache.shape[3] == D,
+         "paged cache")
+    _req(block_tables.dtype == torch.int32 and block_tables.shape[0] >= B, "block_tables")
+    _req(kv_lens.dtype == torch.int32, "kv_lens int32")
+    _req(Hq // Hkv <= 16, "G <= 16")
+    if max_parts > 1:
+        if ws_o is None:
+            ws_o = torch.empty((B, Hq, max_parts, D), dtype=torch.float32, device=dev)
+            ws_ml = torch.empty((B, Hq, max_parts, 2), dtype=torch.float32, device=dev)
+        _req(ws_o.numel() >= B * Hq * max_parts * D and ws_ml.numel() >= B * Hq * max_parts * 2, "workspace")
+    if defer_merge:  # the partitions stay unmerged for gemm_part_merge (no reduce launch)
+        _req(max_parts > 1 and ws_o is not None, "deferred merge needs a partition workspace")
+    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    P, positions, slots, cos_t, sin_t = rope or (None,) * 5
+    kd, vd = (k_cache.data, v_cache.data) if f8 else (k_cache, v_cache)
+    ks, vs = (k_cache.scale, v_cache.scale) if f8 else (None, None)
+    check(_lib.lib().ragk_attn_decode(
+        ptr(q), q.stride(0) if q is not None else 0, ptr(P), P.shape[0] if rope else 0, P.shape[2] if rope else 0,
+        ptr(positions), ptr(slots), ptr(cos_t), ptr(sin_t), kd.data_ptr(), vd.data_ptr(), ptr(ks), ptr(vs),
+        block_tables.data_ptr(), block_tables.stride(0), kv_lens.data_ptr(), ptr(ws_o), ptr(ws_ml), out.data_ptr(),
+        out.stride(0), B, Hq, Hkv, D, part_tiles, max_parts, float(scale), decode_flags(B, Hkv, defer_merge),
+        stream_ptr()), "ragk_attn_decode")
+    return out
 
 
 def attn_decode(q, k_cache, v_cache, block_tables, kv_lens, out, Hq, Hkv, D, part_tiles, max_parts, ws_o=None,
                 ws_ml=None, scale=None):
-    B = kv_lens.numel()
-    f8 = isinstance(k_cache, Fp8KV) or isinstance(v_cache, Fp8KV)
-    if f8:
-        _kv8(k_cache, v_cache, Hkv, D, q.device)
-    _req(len(k_cache.shape) == 4 and k_cache.shape[2] == 64 and k_cache.shape[3] == D, "paged cache")
-    _req(block_tables.dtype == torch.int32 and block_tables.shape[0] >= B, "block_tables")
-    _req(kv_lens.dtype == torch.int32, "kv_lens int32")
-    G = Hq // Hkv
-    _req(G <= 16, "G <= 16")
-    if max_parts > 1:
-        if ws_o is None:
-            ws_o = torch.empty((B, Hq, max_parts, D), dtype=torch.float32, device=q.device)
-            ws_ml = torch.empty((B, Hq, max_parts, 2), dtype=torch.float32, device=q.device)
-        _req(ws_o.numel() >= B * Hq * max_parts * D and ws_ml.numel() >= B * Hq * max_parts * 2, "workspace")
-    scale = 1.0 / math.sqrt(D) if scale is None else scale
-    _set_decode_nt(B, Hkv)
-    if f8:
-        check(_lib.lib().ragk_attn_decode_fp8(
-            q.data_ptr(), q.stride(0), k_cache.data.data_ptr(), v_cache.data.data_ptr(), k_cache.scale.data_ptr(),
-            v_cache.scale.data_ptr(), block_tables.data_ptr(), block_tables.stride(0), kv_lens.data_ptr(), ptr(ws_o),
-            ptr(ws_ml), out.data_ptr(), out.stride(0), B, Hq, Hkv, D, part_tiles, max_parts, float(scale),
-            stream_ptr()), "ragk_attn_decode_fp8")
-        return out
-    check(_lib.lib().ragk_attn_decode(
-        q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), block_tables.data_ptr(),
-        block_tables.stride(0), kv_lens.data_ptr(), ptr(ws_o), ptr(ws_ml), out.data_ptr(), out.stride(0), B, Hq, Hkv,
-        D, part_tiles, max_parts, float(scale), stream_ptr()), "ragk_attn_decode")
-    return out
+    return _launch_attn_decode(q, None, k_cache, v_cache, block_tables, kv_lens, out, Hq, Hkv, D, part_tiles,
+                               max_parts, ws_o, ws_ml, scale)
 
 
 def attn_decode_rope(P, positions, cos_t, sin_t, slots, k_cache, v_cache, block_tables, kv_lens, out, Hq, Hkv, D,
@@ -1316,44 +1322,8 @@ def attn_decode_rope(P, positions, cos_t, sin_t, slots, k_cache, v_cache, block_
     _req(kv_lens.numel() == B, "one partial row per sequence")
     _req(positions.dtype == torch.int32 and positions.numel() == B, "positions")
     _req(slots is not None and slots.dtype == torch.int32 and slots.numel() == B, "slots")
-    f8 = isinstance(k_cache, Fp8KV) or isinstance(v_cache, Fp8KV)
-    if f8:
-        _kv8(k_cache, v_cache, Hkv, D, P.device)
-    _req(len(k_cache.shape) == 4 and k_cache.shape[1] == Hkv and k_cache.shape[2] == 64 and k_cache.shape[3] == D,
-         "paged cache")
-    _req(block_tables.dtype == torch.int32 and block_tables.shape[0] >= B, "block_tables")
-    _req(kv_lens.dtype == torch.int32, "kv_lens int32")
-    _req(Hq // Hkv <= 16, "G <= 16")
-    if max_parts > 1:
-        if ws_o is None:
-            ws_o = torch.empty((B, Hq, max_parts, D), dtype=torch.float32, device=P.device)
-            ws_ml = torch.empty((B, Hq, max_parts, 2), dtype=torch.float32, device=P.device)
-        _req(ws_o.numel() >= B * Hq * max_parts * D and ws_ml.numel() >= B * Hq * max_parts * 2, "workspace")
-    scale = 1.0 / math.sqrt(D) if scale is None else scale
-    if defer_merge:  # the partitions stay unmerged for gemm_part_merge (no reduce launch)
-        _req(max_parts > 1 and ws_o is not None, "deferred merge needs a partition workspace")
-    lib = _lib.lib()
-    _set_decode_nt(B, Hkv)
-    if defer_merge:
-        lib.ragk_attn_decode_set_defer(1)
-    try:
-        if f8:
-            check(lib.ragk_attn_decode_rope_fp8(
-                P.data_ptr(), S, ldp, positions.data_ptr(), slots.data_ptr(), cos_t.data_ptr(), sin_t.data_ptr(),
-                k_cache.data.data_ptr(), v_cache.data.data_ptr(), k_cache.scale.data_ptr(), v_cache.scale.data_ptr(),
-                block_tables.data_ptr(), block_tables.stride(0), kv_lens.data_ptr(), ptr(ws_o), ptr(ws_ml),
-                out.data_ptr(), out.stride(0), B, Hq, Hkv, D, part_tiles, max_parts, float(scale), stream_ptr()),
-                "ragk_attn_decode_rope_fp8")
-        else:
-            check(lib.ragk_attn_decode_rope(
-                P.data_ptr(), S, ldp, positions.data_ptr(), slots.data_ptr(), cos_t.data_ptr(), sin_t.data_ptr(),
-                k_cache.data_ptr(), v_cache.data_ptr(), block_tables.data_ptr(), block_tables.stride(0),
-                kv_lens.data_ptr(), ptr(ws_o), ptr(ws_ml), out.data_ptr(), out.stride(0), B, Hq, Hkv, D, part_tiles,
-                max_parts, float(scale), stream_ptr()), "ragk_attn_decode_rope")
-    finally:
-        if defer_merge:
-            lib.ragk_attn_decode_set_defer(0)
-    return out
+    return _launch_attn_decode(None, (P, positions, slots, cos_t, sin_t), k_cache, v_cache, block_tables, kv_lens, out,
+                               Hq, Hkv, D, part_tiles, max_parts, ws_o, ws_ml, scale, defer_merge)
 
 
 # ----------------------------------------------------------------------------- sampling

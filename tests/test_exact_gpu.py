@@ -406,8 +406,7 @@ def test_add_partials_rmsnorm_leading_dimensions(native):
 class _NoLaunch:
     """Stands in for the kernel library while misaligned operands are offered: host-side queries pass through,
     anything that could launch fails the test instead of running."""
-    HOST = {"ragk_gemm_part_ksteps", "ragk_gemm_part_set_min_blocks", "ragk_gemm_stream_splits",
-            "ragk_gemm_dec_splits"}
+    HOST = {"ragk_gemm_part_ksteps", "ragk_gemm_stream_splits", "ragk_gemm_dec_splits"}
 
     def __init__(self, real):
         self._real = real

@@ -543,6 +543,93 @@ def test_attn_decode_rope_matches_unfused(native, kv_lens, target, Hq, Hkv):
     assert torch.equal(out, ref)
 
 
+def test_attn_decode_policy_does_not_outlive_its_call(native):
+    """The launch policy of a decode-attention call is an argument of that call: a deferred-merge launch leaves
+    nothing behind for the next one. 3 and 9 KV tiles over max_parts = 3 (sequence 0 takes one partition and is
+    written by the partition kernel, sequence 1 takes three), plain / deferred / plain on identical inputs: the
+    plain outputs and all three partition workspaces are equal bit for bit (the flag only drops the reduce
+    launch); then attn_decode (no rope) after a deferred launch == the same call made before it."""
+    D, S, Hq, Hkv = 128, 4, 8, 2
+    kv_lens = [130, 517]
+    torch.manual_seed(23)
+    kc0, vc0, bt = _paged_setup(kv_lens, Hkv, D, seed=9)
+    B = len(kv_lens)
+    kc0, vc0, bt = kc0.to(DEV), vc0.to(DEV), bt.to(DEV)
+    kvl = torch.tensor(kv_lens, dtype=torch.int32, device=DEV)
+    pos = kvl - 1
+    slots = (bt[torch.arange(B, device=DEV), (pos // 64).long()] * 64 + pos % 64).int()
+    P = torch.randn(S, B, (Hq + 2 * Hkv) * D, device=DEV)
+    cos, sin = R.rope_tables(D, 8192, theta=500000.0, scaling=None)
+    cos, sin = cos.to(DEV), sin.to(DEV)
+    pt, mp = native.decode_partitions(640, B, Hkv)
+    assert (pt, mp) == (4, 3)  # min(ceil(512 / 4), ceil(10 / 4)) partitions of at least 4 tiles
+
+    def fresh():  # output and zeroed partition workspaces (single-partition rows leave theirs untouched)
+        return (torch.zeros(B, Hq * D, device=DEV).bfloat16(),
+                torch.zeros((B, Hq, mp, D), dtype=torch.float32, device=DEV),
+                torch.zeros((B, Hq, mp, 2), dtype=torch.float32, device=DEV))
+
+    # q rows and a cache that already holds the new token, for the no-rope calls
+    kcq, vcq = kc0.clone(), vc0.clone()
+    q = torch.empty(B, Hq * D, device=DEV).bfloat16()
+    native.rope_kv_partials(P, q, pos, cos, sin, slots, kcq, vcq, Hq, Hkv, D)
+    first = fresh()
+    native.attn_decode(q, kcq, vcq, bt, kvl, first[0], Hq, Hkv, D, pt, mp, ws_o=first[1], ws_ml=first[2])
+
+    runs = []
+    for defer in (False, True, False):
+        out, ws_o, ws_ml = fresh()
+        native.attn_decode_rope(P, pos, cos, sin, slots, kc0.clone(), vc0.clone(), bt, kvl, out, Hq, Hkv, D, pt, mp,
+                                ws_o=ws_o, ws_ml=ws_ml, defer_merge=defer)
+        runs.append((out, ws_o, ws_ml))
+    torch.cuda.synchronize()
+    assert torch.equal(runs[0][0], runs[2][0])
+    assert bool((runs[0][1][1] != 0).any())  # sequence 1's partition records were written
+    for r in runs[1:]:
+        assert torch.equal(r[1], runs[0][1]) and torch.equal(r[2], runs[0][2])
+    # the deferred launch wrote sequence 0 (one partition) itself and left sequence 1's output row to the consumer
+    assert torch.equal(runs[1][0][0], runs[0][0][0]) and not bool(runs[1][0][1].any())
+
+    out, ws_o, ws_ml = fresh()
+    native.attn_decode_rope(P, pos, cos, sin, slots, kc0.clone(), vc0.clone(), bt, kvl, out, Hq, Hkv, D, pt, mp,
+                            ws_o=ws_o, ws_ml=ws_ml, defer_merge=True)
+    after = fresh()
+    native.attn_decode(q, kcq, vcq, bt, kvl, after[0], Hq, Hkv, D, pt, mp, ws_o=after[1], ws_ml=after[2])
+    torch.cuda.synchronize()
+    for x, y in zip(after, first):
+        assert torch.equal(x, y)
+    assert torch.equal(first[0], runs[0][0])  # and the fused launch == rope_kv_partials + attn_decode
+
+
+def _part_ksteps_rule(M, N, K, min_blocks, legal=(32, 28, 16, 14, 8, 4)):
+    """The slice rule of gemm_part.hip (ragk_gemm_part_ksteps), written out: the widest K-slice (64 * ks) that
+    divides K, fits LDS in whole 8-wave DMA pieces and still gives min_blocks blocks, else the narrowest legal."""
+    mt, nb = (M + 15) // 16, (N + 63) // 64
+    ok = [ks for ks in legal if K % (64 * ks) == 0 and 16 * mt * 64 * ks * 2 <= 128 * 1024
+          and (16 * mt * 64 * ks * 2) % 8192 == 0]
+    for ks in ok:
+        if nb * (K // (64 * ks)) >= min_blocks:
+            return ks
+    return ok[-1] if ok else 0
+
+
+def test_gemm_part_slabs_follows_min_blocks_at_call_time(native, monkeypatch):
+    """PART_MIN_BLOCKS is read on every gemm_part_slabs call (no launch here; the kernel library answers the
+    host-side query): at (1, 4096, 4096) the legal slices are 32 / 16 / 8 / 4 steps, so a threshold of 1 picks
+    the widest and one nothing reaches picks the narrowest, within one process. _silu_ks applies the same rule
+    to its own legal set (16 / 8 / 4 steps) with the same constant."""
+    M, N, K = 1, 4096, 4096
+    assert (_part_ksteps_rule(M, N, K, 1), _part_ksteps_rule(M, N, K, 1 << 30)) == (32, 4)
+    for mb in (1, 1 << 30, 512):
+        monkeypatch.setattr(native, "PART_MIN_BLOCKS", mb)
+        want = _part_ksteps_rule(M, N, K, mb)
+        assert native.gemm_part_slabs(M, N, K) == (want, K // (64 * want)), mb
+        silu = native._silu_ks(M, N, K)
+        assert silu == _part_ksteps_rule(M, N, K, mb, legal=(16, 8, 4)), mb
+        if want <= 16:  # a slice both may take: the two agree
+            assert silu == want, mb
+
+
 @pytest.mark.parametrize("M,N,K,ns", [(5207, 4096, 4096, 2), (5207, 4096, 14336, 2), (300, 4096, 4096, 4),
                                        (1000, 1024, 2048, 2), (256, 520, 1024, 4)])
 def test_gemm_splitk_slabs(native, M, N, K, ns):

@@ -27,7 +27,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main():
     from rag_llm_k8s_amd import _build
-    from rag_llm_k8s_amd.ops import _lib, native
+    from rag_llm_k8s_amd.ops import native
     from rag_llm_k8s_amd.ops.reference import rope_tables
 
     ap = argparse.ArgumentParser()
@@ -87,7 +87,6 @@ def main():
     kv_bytes = sum(lens) * Hkv * (D + 4 if fp8 else D * 2) * 2  # fp8: one byte per element + a 4-byte row scale
     print("kv_dtype=%s B=%d ctx %d..%d (mean %.0f) NL=%d: %.1f MB of KV per launch, part_tiles %d max_parts %d" % (
         "fp8" if fp8 else "bf16", B, min(lens), max(lens), sum(lens) / B, NL, kv_bytes / 1e6, pt, mp), flush=True)
-    L = _lib.lib()
 
     def run():
         for kc, vc in caches:
@@ -114,7 +113,7 @@ def main():
     for v in variants:
         key = v
         if key not in graphs:
-            L.ragk_attn_decode_set_diag({"diag": 1, "diag_dma": 2}.get(v, 0))
+            native.DECODE_DIAG = {"diag": 1, "diag_dma": 2}.get(v, 0)
             kl_default = native.DECODE_KL
             native.DECODE_KL = v == "kl"  # base: the 8-wave kernel with K in registers
             nt_min = native.DECODE_NT_MIN_BH
@@ -130,7 +129,7 @@ def main():
                 run()
             graphs[key] = gr
             native.DECODE_NT_MIN_BH = nt_min
-            L.ragk_attn_decode_set_diag(0)
+            native.DECODE_DIAG = 0
             native.DECODE_KL = kl_default
         gr = graphs[key]
         gr.replay()
