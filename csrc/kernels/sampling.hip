@@ -51,11 +51,13 @@ __device__ void bitonic_desc(float* v, int* ix, int n) {
 
 // Block (row b, vocab chunk c): top-K of logits[b, c*Vc : min((c+1)*Vc, V)] -> candidates
 // [b][c*K + i]; chunking spreads one row over `chunks` workgroups (128k vocab: 16 x 8k).
+// Ties at the K-th value take the lowest vocabulary ids, as the LDS and wave kernels do (the sampler's
+// list merges assume lists in the order value desc, id asc).
 __global__ __launch_bounds__(TK_THREADS) void topk_candidates_kernel(const float* __restrict__ logits, int ld, int Vtot,
                                                                      int K, int vocab_offset, int chunks,
                                                                      float* cand_v, int* cand_i) {
   __shared__ unsigned hist[256];
-  __shared__ unsigned s_prefix, s_krem, s_cnt_gt, s_cnt_eq;
+  __shared__ unsigned s_prefix, s_krem, s_eqtot, s_cnt_gt, s_cnt_eq;
   __shared__ float sv[MAXK];
   __shared__ int si[MAXK];
   const int b = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
@@ -83,30 +85,41 @@ __global__ __launch_bounds__(TK_THREADS) void topk_candidates_kernel(const float
       if (d < 0) d = 0;
       s_prefix = prefix | ((unsigned)d << shift);
       s_krem = krem - above;
+      s_eqtot = hist[d];  // after the last pass: how many keys equal the K-th
     }
     __syncthreads();
     prefix = s_prefix;
     krem = s_krem;
     mask |= 255u << shift;
   }
-  // prefix = key of the K-th largest; take all keys > prefix plus `krem` of those == prefix
+  // prefix = key of the K-th largest: every key > prefix, plus the krem lowest-id keys == prefix
   if (threadIdx.x == 0) { s_cnt_gt = 0; s_cnt_eq = 0; }
   for (int i = threadIdx.x; i < MAXK; i += TK_THREADS) { sv[i] = -INFINITY; si[i] = 0x7fffffff; }
   __syncthreads();
   const int kk = max(0, min(K, V));
   const unsigned n_gt = (unsigned)kk - min(krem, (unsigned)kk);
+  const bool all_eq = s_eqtot == krem;
   for (int i = threadIdx.x; i < V; i += TK_THREADS) {
     const float x = row[i];
     const unsigned k = fkey(x);
     if (k > prefix) {
       const unsigned slot = atomicAdd(&s_cnt_gt, 1u);
       if (slot < (unsigned)MAXK) { sv[slot] = x; si[slot] = i + vocab_offset; }
-    } else if (k == prefix) {
-      const unsigned e = atomicAdd(&s_cnt_eq, 1u);
-      if (e < krem) {
-        const unsigned slot = n_gt + e;
-        if (slot < (unsigned)MAXK) { sv[slot] = x; si[slot] = i + vocab_offset; }
-      }
+    } else if (k == prefix && all_eq) {  // every tie is taken: the sort below orders them
+      const unsigned slot = n_gt + atomicAdd(&s_cnt_eq, 1u);
+      if (slot < (unsigned)MAXK) { sv[slot] = x; si[slot] = i + vocab_offset; }
+    }
+  }
+  if (!all_eq && threadIdx.x < 64) {  // ties beyond the K-th value (rare): the lowest ids, wave 0 in id order
+    const int lane = threadIdx.x;
+    unsigned e = 0;  // ties seen so far (wave-uniform)
+    for (int base = 0; base < V && e < krem; base += 64) {
+      const int i = base + lane;
+      const bool eq = i < V && fkey(row[i]) == prefix;
+      const unsigned long long m = __ballot(eq);
+      const unsigned slot = n_gt + e + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+      if (eq && slot < (unsigned)kk) { sv[slot] = row[i]; si[slot] = i + vocab_offset; }
+      e += (unsigned)__popcll(m);
     }
   }
   __syncthreads();
