@@ -47,6 +47,12 @@ class RagConfig:
     repetition_penalty: float = 1.0
     no_repeat_ngram_size: int = 0
     min_new_tokens: int = 0
+    # OpenAI-style controls of the same family (off by default; JSON fields of the same names override them):
+    # presence / frequency penalties in -2..2 over the generated tokens, and a logit bias as a JSON object
+    # string {"<token id>": bias in -100..100, ...} of at most 300 entries
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    logit_bias: str = ""
     # per-token log-probabilities with this many alternatives (0..20) in every response; None (unset) = off.
     # A /generate request may set "logprobs" itself.
     logprobs: Optional[int] = None
@@ -99,6 +105,8 @@ class RagConfig:
             "TEMPERATURE": ("temperature", float), "TOP_P": ("top_p", float), "TOP_K": ("top_k", int),
             "REPETITION_PENALTY": ("repetition_penalty", float), "NO_REPEAT_NGRAM_SIZE": ("no_repeat_ngram_size", int),
             "MIN_NEW_TOKENS": ("min_new_tokens", int), "LOGPROBS": ("logprobs", int),
+            "PRESENCE_PENALTY": ("presence_penalty", float), "FREQUENCY_PENALTY": ("frequency_penalty", float),
+            "LOGIT_BIAS": ("logit_bias", str),
             "SEED": ("seed", int), "TP_SIZE": ("tp_size", int), "DTYPE": ("dtype", str), "DEVICE": ("device", str),
             "INDEX_TYPE": ("index_type", str), "IVF_NLIST": ("ivf_nlist", int), "IVF_NPROBE": ("ivf_nprobe", int),
             "REINGEST_APPEND": ("reingest_append", bool), "MAX_BATCH": ("max_batch", int),

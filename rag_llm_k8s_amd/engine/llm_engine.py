@@ -37,6 +37,9 @@ from ..ops.backend import AttnMeta
 from ..ops.fp8 import kv_cache_dtype_name, kv_cache_torch_dtype
 # per-token log-probabilities (csrc/kernels/logprobs.hip): LOGPROBS_MAX = most alternatives per position
 from ..ops.reference import LOGPROBS_MAX, lse_chunks
+# logit_bias entries per request, and the most tokens a request with a frequency / presence penalty may generate
+# (the LDS counting table of csrc/kernels/logits_proc.hip)
+from ..ops.reference import LOGIT_BIAS_MAX, PENALTY_GEN_MAX
 from ..utils import faults
 from .kv_manager import BLOCK, make_block_manager
 
@@ -74,10 +77,41 @@ class SamplingParams:
     # alternatives, log_softmax of the fp32 logits after the processors above and before temperature / top-k /
     # top-p (transformers' `scores` of a greedy generate; the unwarped model distribution for sampled requests)
     logprobs: Optional[int] = None
+    # OpenAI-style controls, applied with the processors above (ops/reference.py logits_process): logit_bias
+    # first, then the repetition penalty, then frequency and presence over the GENERATED tokens only
+    # (x - frequency * count - presence for every generated id), then the -inf bans. 0.0 / () mean off.
+    presence_penalty: float = 0.0  # -2..2
+    frequency_penalty: float = 0.0  # -2..2
+    logit_bias: tuple = ()  # ((token id, bias in -100..100), ...) sorted by id, at most LOGIT_BIAS_MAX
+
+    def uses_penalties(self) -> bool:
+        return self.presence_penalty != 0.0 or self.frequency_penalty != 0.0 or len(self.logit_bias) > 0
 
     def uses_processors(self) -> bool:
         return (self.repetition_penalty != 1.0 or self.no_repeat_ngram_size > 0
-                or (self.min_new_tokens > 0 and not self.ignore_eos))
+                or (self.min_new_tokens > 0 and not self.ignore_eos) or self.uses_penalties())
+
+
+def normalize_logit_bias(bias) -> tuple:
+    """SamplingParams.logit_bias from a mapping {id: bias} or an iterable of (id, bias) pairs: a tuple of
+    (int id, float bias) sorted by id. Raises ValueError for an id that is not an integer, a value that is not a
+    number, or a duplicate id; ranges are check_params' business."""
+    items = list(bias.items()) if hasattr(bias, "items") else [tuple(e) for e in bias]
+    out = []
+    for e in items:
+        if len(e) != 2:
+            raise ValueError("logit_bias entries are (token id, bias) pairs (got %r)" % (e,))
+        t, v = e
+        if isinstance(t, bool) or not isinstance(t, (int, np.integer)):
+            raise ValueError("logit_bias: token id %r is not an integer" % (t,))
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError("logit_bias: the bias of token %d must be a number (got %r)" % (t, v))
+        out.append((int(t), float(v)))
+    out.sort()
+    for a, b in zip(out, out[1:]):
+        if a[0] == b[0]:
+            raise ValueError("logit_bias: token id %d occurs twice" % a[0])
+    return tuple(out)
 
 
 WAITING, RUNNING, FINISHED = 0, 1, 2
@@ -204,6 +238,7 @@ class LLMEngine:
         self._hist_free = None
         self._hist_after = []
         self.stats["logit_proc_steps"] = 0
+        self.stats["penalty_steps"] = 0  # of those: steps with a row that uses presence / frequency / logit_bias
         # per-token log-probabilities: steps that had a row asking for them, and the two pinned read-back
         # buffers of the asynchronous pipeline (allocated at the first such step, alternated like _out_pins)
         self.stats["logprob_steps"] = 0
@@ -254,6 +289,27 @@ class LLMEngine:
             if LOGPROBS_MAX > self.K:
                 raise ValueError("logprobs: the engine's candidate lists (top_k_cap = %d) are shorter than %d"
                                  % (self.K, LOGPROBS_MAX))
+        for name in ("presence_penalty", "frequency_penalty"):
+            v = getattr(p, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not -2 <= v <= 2:
+                raise ValueError("%s must be a finite number in -2..2 (got %r)" % (name, v))
+        lb = p.logit_bias
+        if not isinstance(lb, tuple):
+            raise ValueError("logit_bias must be a tuple of (token id, bias) pairs sorted by id (normalize_logit_bias)")
+        if len(lb) > LOGIT_BIAS_MAX:
+            raise ValueError("logit_bias: at most %d entries (got %d)" % (LOGIT_BIAS_MAX, len(lb)))
+        if lb:
+            if normalize_logit_bias(lb) != lb:
+                raise ValueError("logit_bias must hold (int id, float bias) pairs sorted by id (normalize_logit_bias)")
+            vocab = int(self.model.cfg.vocab_size)  # the whole vocabulary, not this rank's shard
+            for t, v in lb:
+                if not 0 <= t < vocab:
+                    raise ValueError("logit_bias: token id %d outside the vocabulary 0..%d" % (t, vocab - 1))
+                if not math.isfinite(v) or not -100 <= v <= 100:
+                    raise ValueError("logit_bias: the bias of token %d must be finite, in -100..100 (got %r)" % (t, v))
+        if (p.presence_penalty != 0.0 or p.frequency_penalty != 0.0) and p.max_new_tokens > PENALTY_GEN_MAX:
+            raise ValueError("presence_penalty / frequency_penalty: max_new_tokens %d exceeds the %d generated "
+                             "tokens the penalties count" % (p.max_new_tokens, PENALTY_GEN_MAX))
         if p.uses_processors() and self.is_cuda:
             from ..ops.native import logits_proc_max_hist
             if self.max_model_len > logits_proc_max_hist():
@@ -266,6 +322,26 @@ class LLMEngine:
             self._hist = torch.zeros((max(1, self.max_batch), self.max_model_len), dtype=torch.int32,
                                      device=self.device)
             self._hist_free = list(range(self._hist.shape[0] - 1, -1, -1))
+            # logit_bias tables, one row per history row: written once when a sequence takes the row
+            # (_write_bias), read by the kernel up to the row's bias count of that step's argument block
+            self._bias_ids = torch.zeros((self._hist.shape[0], LOGIT_BIAS_MAX), dtype=torch.int32, device=self.device)
+            self._bias_vals = torch.zeros((self._hist.shape[0], LOGIT_BIAS_MAX), dtype=torch.float32,
+                                          device=self.device)
+
+    def _write_bias(self, s):
+        """The sequence's logit_bias into its history row's table row: stream-ordered copies on the compute
+        stream. No in-flight step reads the row (a finished sequence's row is released only after the step that
+        could still touch it has completed), and a sequence without a bias passes count 0, so nothing of the
+        row's previous owner is ever read."""
+        lb = s.params.logit_bias
+        if not lb:
+            return
+        n = len(lb)
+        ids = np.fromiter((t for t, _ in lb), dtype=np.int32, count=n)
+        vals = np.fromiter((v for _, v in lb), dtype=np.float32, count=n)
+        buf = self._h2d_i32(np.concatenate([ids, vals.view(np.int32)]))
+        self._bias_ids[s.hist_row, :n].copy_(buf[:n], non_blocking=True)
+        self._bias_vals[s.hist_row, :n].copy_(buf[n:].view(torch.float32), non_blocking=True)
 
     def _free_deferred(self):
         """The in-flight step that could still write them has completed: release the KV blocks and history
@@ -277,9 +353,17 @@ class LLMEngine:
             self._hist_free.extend(self._hist_after)
             self._hist_after = []
 
-    def _proc_host(self, seqs, gen, pad_to=None):
+    PEN_WORDS = 4  # per-row words of the penalty form: gen_start | presence (f32) | frequency (f32) | bias count
+
+    @staticmethod
+    def _uses_penalties(seqs):
+        """True if a row of the step needs the penalty form of the processor launch."""
+        return any(s.hist_row >= 0 and s.params.uses_penalties() for s in seqs)
+
+    def _proc_host(self, seqs, gen, pad_to=None, penalties=False):
         """int32 [(4 + BAN_IDS_MAX) n] = history rows | penalty (f32) | n-gram size | ban count | ban ids [n, W].
-        gen[i]: tokens sequence i has generated before the one being sampled. Plain and padded rows: row -1."""
+        gen[i]: tokens sequence i has generated before the one being sampled. Plain and padded rows: row -1.
+        penalties: PEN_WORDS * n more words, gen_start (the prompt length) | presence | frequency | bias count."""
         n = pad_to or len(seqs)
         rows = np.full(n, -1, dtype=np.int32)
         pen = np.ones(n, dtype=np.float32)
@@ -295,30 +379,61 @@ class LLMEngine:
                 stop = self._stop_ids(p)
                 cnt[i] = len(stop)
                 ban[i, :len(stop)] = stop
-        return np.concatenate([rows, pen.view(np.int32), ng, cnt, ban.reshape(-1)])
+        parts = [rows, pen.view(np.int32), ng, cnt, ban.reshape(-1)]
+        if penalties:
+            g0 = np.zeros(n, dtype=np.int32)
+            pres = np.zeros(n, dtype=np.float32)
+            freq = np.zeros(n, dtype=np.float32)
+            nbias = np.zeros(n, dtype=np.int32)
+            for i, s in enumerate(seqs):
+                if s.hist_row < 0:
+                    continue
+                p = s.params
+                g0[i], pres[i], freq[i], nbias[i] = len(s.prompt), p.presence_penalty, p.frequency_penalty, \
+                    len(p.logit_bias)
+            parts += [g0, pres.view(np.int32), freq.view(np.int32), nbias]
+        return np.concatenate(parts)
 
     @staticmethod
-    def _proc_views(buf, n):
-        return dict(rows=buf[0:n], penalty=buf[n:2 * n].view(torch.float32), ngram=buf[2 * n:3 * n],
-                    ban_count=buf[3 * n:4 * n], ban_ids=buf[4 * n:(4 + BAN_IDS_MAX) * n].view(n, BAN_IDS_MAX))
+    def _proc_views(buf, n, penalties=False):
+        v = dict(rows=buf[0:n], penalty=buf[n:2 * n].view(torch.float32), ngram=buf[2 * n:3 * n],
+                 ban_count=buf[3 * n:4 * n], ban_ids=buf[4 * n:(4 + BAN_IDS_MAX) * n].view(n, BAN_IDS_MAX))
+        if penalties:
+            o = (4 + BAN_IDS_MAX) * n
+            v.update(gen_start=buf[o:o + n], presence=buf[o + n:o + 2 * n].view(torch.float32),
+                     frequency=buf[o + 2 * n:o + 3 * n].view(torch.float32), bias_count=buf[o + 3 * n:o + 4 * n])
+        return v
 
     def _proc_tensors(self, seqs, pos, gen, ids=None):
         """Processor argument block of an eager sampling call (None if no row of it has a history row).
         pos[i]: position of sequence i's last token (history length - 1); ids: decode input ids, stored into
-        the history by the kernel, or None when the history is already complete (prefill's sampled rows)."""
+        the history by the kernel, or None when the history is already complete (prefill's sampled rows). A
+        call with a row that uses the penalty fields carries their words too (the penalty form of the launch)."""
         if not any(s.hist_row >= 0 for s in seqs):
             return None
         n = len(seqs)
-        buf = self._h2d_i32(np.concatenate([self._proc_host(seqs, gen), np.asarray(pos, dtype=np.int32)]))
-        proc = self._proc_views(buf, n)
-        proc["pos"] = buf[(4 + BAN_IDS_MAX) * n:(5 + BAN_IDS_MAX) * n]
+        pen = self._uses_penalties(seqs)
+        buf = self._h2d_i32(np.concatenate([self._proc_host(seqs, gen, penalties=pen),
+                                            np.asarray(pos, dtype=np.int32)]))
+        proc = self._proc_views(buf, n, penalties=pen)
+        o = (4 + BAN_IDS_MAX + (self.PEN_WORDS if pen else 0)) * n
+        proc["pos"] = buf[o:o + n]
         proc["ids"] = ids
         return proc
 
     def _apply_processors(self, lg, proc):
         be = self.model.be
+        if "gen_start" not in proc:
+            be.logits_process(lg, self.model.w.vocab_offset, proc["ids"], proc["rows"], proc["pos"], self._hist,
+                              proc["penalty"], proc["ngram"], proc["ban_ids"], proc["ban_count"])
+            return
+        # the penalty form. Admission bounds a penalised request's generated tokens by PENALTY_GEN_MAX; the
+        # bound is a host constant, so the launch is the same at capture and at every replay
         be.logits_process(lg, self.model.w.vocab_offset, proc["ids"], proc["rows"], proc["pos"], self._hist,
-                          proc["penalty"], proc["ngram"], proc["ban_ids"], proc["ban_count"])
+                          proc["penalty"], proc["ngram"], proc["ban_ids"], proc["ban_count"],
+                          gen_start=proc["gen_start"], presence=proc["presence"], frequency=proc["frequency"],
+                          bias_ids=self._bias_ids, bias_vals=self._bias_vals, bias_count=proc["bias_count"],
+                          gen_bound=min(PENALTY_GEN_MAX, self.max_model_len))
 
     # ------------------------------------------------------------------ per-token log-probabilities
     LP_WORDS = 2 + 2 * LOGPROBS_MAX  # output words per row: lse | token logprob | top logprobs | top ids
@@ -406,6 +521,7 @@ class LLMEngine:
                     if not self._hist_free:
                         break
                     s.hist_row = self._hist_free.pop()
+                    self._write_bias(s)
                 self.waiting.popleft()
                 self.bm.ensure(s.id, need)
                 s.status = RUNNING
@@ -834,6 +950,7 @@ class LLMEngine:
             if out_seqs else None
         if proc is not None:
             self.stats["logit_proc_steps"] += 1
+            self.stats["penalty_steps"] += int("gen_start" in proc)
         # the first generated token's logprobs: the same two launches on this eager sampling call
         vals = None
         if out_seqs and self._needs_full_vocab(out_seqs):
@@ -903,14 +1020,20 @@ class LLMEngine:
             kvl[:n] = p + 1
         return out
 
-    def _decode_graph(self, B, with_processors=False, with_logprobs=False):
+    def _decode_graph(self, B, with_processors=False, with_logprobs=False, with_penalties=False):
         """Decode graph of batch bucket B, keyed (B, with_processors). The plain entry is what every step of
         requests without logit processors replays; the processor variant (captured lazily, like any bucket)
         adds the processor kernel between lm_head and the top-k and appends its per-row argument block to the
         packed buffer. A step in which some row wants logprobs replays a further variant keyed
         (B, with_processors, True): the two logprob launches around the sampler, the rows' alternative counts
-        (nlp) as the last B words of the packed buffer, and entry["lp"]["buf"] as the values' device buffer."""
+        (nlp) as the last B words of the packed buffer, and entry["lp"]["buf"] as the values' device buffer.
+        A step in which some row uses presence / frequency penalties or a logit_bias replays a variant of its
+        own, keyed (B, True, with_logprobs, True): the penalty form of the processor launch, PEN_WORDS more
+        words per row after the ban ids. The entries under the keys above are what they were without it."""
         key = (B, bool(with_processors)) + ((True,) if with_logprobs else ())
+        if with_penalties:
+            with_processors = True
+            key = (B, True, bool(with_logprobs), True)
         if key in self.graphs:
             return self.graphs[key]
         from ..ops.native import decode_partitions
@@ -922,7 +1045,7 @@ class LLMEngine:
         # ONE H2D copy per step: [decode metadata | sampling params (6B) | carry map (B)]
         # (+ with processors: [history rows | penalty | n-gram size | ban count | ban ids (B x BAN_IDS_MAX)])
         # (+ with logprobs: [alternatives per row (B)])
-        proc_n = (4 + BAN_IDS_MAX) * B if with_processors else 0
+        proc_n = (4 + BAN_IDS_MAX + (self.PEN_WORDS if with_penalties else 0)) * B if with_processors else 0
         packed = torch.zeros(meta_n + 7 * B + proc_n + (B if with_logprobs else 0), dtype=torch.int32, device=dev)
         ids, pos, slots, kvl = (packed[i * B:(i + 1) * B] for i in range(4))
         carry = packed[meta_n + 6 * B:meta_n + 7 * B]
@@ -940,7 +1063,7 @@ class LLMEngine:
         if with_processors:
             # the kernel stores ids[b] (already resolved by the embedding kernel for carried rows) at
             # hist[row][pos[b]] before it reads the row's history
-            proc = self._proc_views(packed[meta_n + 7 * B:meta_n + 7 * B + proc_n], B)
+            proc = self._proc_views(packed[meta_n + 7 * B:meta_n + 7 * B + proc_n], B, penalties=with_penalties)
             proc["ids"], proc["pos"] = ids, pos
         lp = None
         if with_logprobs:
@@ -1033,7 +1156,8 @@ class LLMEngine:
         B = self._bucket(n)
         with_proc = any(s.hist_row >= 0 for s in seqs)
         with_lp = any(s.logprobs is not None for s in seqs)
-        e = self._decode_graph(B, with_proc, with_lp)
+        with_pen = with_proc and self._uses_penalties(seqs)
+        e = self._decode_graph(B, with_proc, with_lp, with_pen)
         samp = self._sampling_host(seqs, pad_to=B)
         steps = samp[5 * B:5 * B + n]
         steps += np.asarray(carried, dtype=np.int32)  # sampling step index of the token being produced
@@ -1045,8 +1169,10 @@ class LLMEngine:
         if with_proc:
             # tokens generated before the one this step samples: a carried row's in-flight token counts, as
             # in `steps` above
-            parts.append(self._proc_host(seqs, [len(s.out) + int(c) for s, c in zip(seqs, carried)], pad_to=B))
+            parts.append(self._proc_host(seqs, [len(s.out) + int(c) for s, c in zip(seqs, carried)], pad_to=B,
+                                         penalties=with_pen))
             self.stats["logit_proc_steps"] += 1
+            self.stats["penalty_steps"] += int(with_pen)
         if with_lp:
             parts.append(self._lp_host(seqs, pad_to=B))
             self.stats["logprob_steps"] += 1
@@ -1186,18 +1312,20 @@ class LLMEngine:
             return finished
         gen = [len(s.out) for s in seqs]
         with_proc = any(s.hist_row >= 0 for s in seqs)
+        with_pen = with_proc and self._uses_penalties(seqs)
         if with_proc:
             self.stats["logit_proc_steps"] += 1
+            self.stats["penalty_steps"] += int(with_pen)
         with_lp = any(s.logprobs is not None for s in seqs)
         vals = None
         if self.is_cuda:
             B = self._bucket(n)
             # a full-vocabulary step computes its logprobs on the host: it needs no graph variant
-            e = self._decode_graph(B, with_proc, with_lp and not full_vocab)
+            e = self._decode_graph(B, with_proc, with_lp and not full_vocab, with_pen)
             parts = [self._decode_inputs_host(seqs, B), self._sampling_host(seqs, pad_to=B),
                      np.full(B, -1, dtype=np.int32)]
             if with_proc:
-                parts.append(self._proc_host(seqs, gen, pad_to=B))
+                parts.append(self._proc_host(seqs, gen, pad_to=B, penalties=with_pen))
             if with_lp and not full_vocab:
                 parts.append(self._lp_host(seqs, pad_to=B))
             if with_lp:

@@ -80,6 +80,9 @@ _SIGS = {
     "ragk_logits_proc_max_hist": [],
     "ragk_hist_write": [P, P, P, P, I, I, I, S],
     "ragk_logits_process": [P, I, I, I, I, P, P, P, P, I, I, P, P, P, I, P, S],
+    "ragk_logits_proc_pen_gen_max": [],
+    "ragk_logits_proc_bias_max": [],
+    "ragk_logits_process_pen": [P, I, I, I, I, P, P, P, P, I, I, P, P, P, I, P, P, P, P, P, P, P, I, I, S],
     # csrc/kernels/logprobs.hip (per-token log-probabilities with top-N alternatives)
     "ragk_logprobs_max": [],
     "ragk_lse_partials": [P, I, I, I, I, P, S],

@@ -259,8 +259,12 @@ class TorchBackend:
     def hist_write(self, ids, rows, pos, hist):
         return R.hist_write(ids, rows, pos, hist)
 
-    def logits_process(self, logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, ban_ids, ban_count):
-        return R.logits_process(logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, ban_ids, ban_count)
+    def logits_process(self, logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, ban_ids, ban_count, *,
+                       gen_start=None, presence=None, frequency=None, bias_ids=None, bias_vals=None, bias_count=None,
+                       gen_bound=None):
+        return R.logits_process(logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, ban_ids, ban_count,
+                                gen_start=gen_start, presence=presence, frequency=frequency, bias_ids=bias_ids,
+                                bias_vals=bias_vals, bias_count=bias_count, gen_bound=gen_bound)
 
     # per-token log-probabilities: lse partials per vocab chunk, then the per-row merge -----------------
     def lse_partials(self, logits, chunks, out=None):
@@ -436,8 +440,12 @@ class NativeBackend(TorchBackend):
     def hist_write(self, ids, rows, pos, hist):
         return self.n.hist_write(ids, rows, pos, hist)
 
-    def logits_process(self, logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, ban_ids, ban_count):
-        return self.n.logits_process(logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, ban_ids, ban_count)
+    def logits_process(self, logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, ban_ids, ban_count, *,
+                       gen_start=None, presence=None, frequency=None, bias_ids=None, bias_vals=None, bias_count=None,
+                       gen_bound=None):
+        return self.n.logits_process(logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, ban_ids, ban_count,
+                                     gen_start=gen_start, presence=presence, frequency=frequency, bias_ids=bias_ids,
+                                     bias_vals=bias_vals, bias_count=bias_count, gen_bound=gen_bound)
 
     def lse_partials(self, logits, chunks, out=None):
         return self.n.lse_partials(logits, chunks, out=out)

@@ -1407,11 +1407,26 @@ def hist_write(ids, rows, pos, hist):
     return hist
 
 
-def logits_process(logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, ban_ids, ban_count):
+def logits_proc_pen_gen_max():
+    """Generated tokens per row the frequency / presence counting table holds at load 1/2 (kernel constant)."""
+    return int(_lib.lib().ragk_logits_proc_pen_gen_max())
+
+
+def logits_process(logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, ban_ids, ban_count, *, gen_start=None,
+                   presence=None, frequency=None, bias_ids=None, bias_vals=None, bias_count=None, gen_bound=None,
+                   check_rows=None):
     """Repetition penalty, n-gram ban and min_new_tokens ban list, in place on fp32 logits [B, V] (a vocab shard
     starting at vocab_offset). One workgroup per row; row b reads hist[rows[b], :pos[b] + 1] (rows[b] < 0: the
     row is not touched). With `ids` (decode) hist[rows[b], pos[b]] = ids[b] is stored first. The kernel stages
-    a whole history row in LDS: a hist wider than logits_proc_max_hist() is refused here."""
+    a whole history row in LDS: a hist wider than logits_proc_max_hist() is refused here.
+
+    With the keyword arguments (ops/reference.py logits_process: logit_bias, frequency and presence penalties)
+    the launch is ragk_logits_process_pen; with all of them None it is ragk_logits_process, as before. gen_bound
+    (host int, default the kernel's maximum) bounds pos - gen_start + 1 of the rows with a penalty: it sizes the
+    LDS counting table, and a bound over logits_proc_pen_gen_max() is refused. The per-row values live on the
+    device: they are read back and checked here (a gen_start outside 0..pos + 1, a penalised span over the bound
+    or a bias_count wider than the table is refused before the launch) unless check_rows is False or, by default,
+    the stream is capturing a graph, where nothing can be read back; the kernel clamps all three itself."""
     _req(logits.dtype == torch.float32 and logits.is_cuda and logits.dim() == 2 and logits.stride(1) == 1, "logits fp32")
     B, V = logits.shape
     dev = logits.device
@@ -1428,11 +1443,33 @@ def logits_process(logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, b
     _req(ban_ids.dtype == torch.int32 and ban_ids.is_cuda and ban_ids.device == dev and ban_ids.dim() == 2
          and ban_ids.shape[0] == B and ban_ids.shape[1] >= 1 and ban_ids.is_contiguous(),
          "ban_ids must be a contiguous int32 [B, width] tensor")
-    check(_lib.lib().ragk_logits_process(logits.data_ptr(), logits.stride(0) if B > 1 else max(V, logits.stride(0)),
-                                         B, V, int(vocab_offset), ptr(ids), rows.data_ptr(), pos.data_ptr(),
-                                         hist.data_ptr(), hist.shape[0], hist.shape[1], penalty.data_ptr(),
-                                         ngram.data_ptr(), ban_ids.data_ptr(), ban_ids.shape[1],
-                                         ban_count.data_ptr(), stream_ptr()), "ragk_logits_process")
+    ld = logits.stride(0) if B > 1 else max(V, logits.stride(0))
+    new = (gen_start, presence, frequency, bias_ids, bias_vals, bias_count)
+    if all(a is None for a in new) and gen_bound is None:
+        check(_lib.lib().ragk_logits_process(logits.data_ptr(), ld, B, V, int(vocab_offset), ptr(ids),
+                                             rows.data_ptr(), pos.data_ptr(), hist.data_ptr(), hist.shape[0],
+                                             hist.shape[1], penalty.data_ptr(), ngram.data_ptr(), ban_ids.data_ptr(),
+                                             ban_ids.shape[1], ban_count.data_ptr(), stream_ptr()),
+              "ragk_logits_process")
+        return logits
+    from .reference import check_penalty_args
+    for t in new:
+        _req(t is None or (t.is_cuda and t.device == dev), "penalty / bias arguments must be on the launch device")
+    if check_rows is None:
+        check_rows = not torch.cuda.is_current_stream_capturing()
+    if check_rows and all(a is not None for a in new):
+        bound = check_penalty_args(B, rows.cpu(), pos.cpu(), hist, gen_start.cpu(), presence.cpu(), frequency.cpu(),
+                                   bias_ids, bias_vals, bias_count.cpu(), gen_bound)
+    else:
+        bound = check_penalty_args(B, rows, pos, hist, gen_start, presence, frequency, bias_ids, bias_vals,
+                                   bias_count, gen_bound, read_rows=False)
+    check(_lib.lib().ragk_logits_process_pen(logits.data_ptr(), ld, B, V, int(vocab_offset), ptr(ids), rows.data_ptr(),
+                                             pos.data_ptr(), hist.data_ptr(), hist.shape[0], hist.shape[1],
+                                             penalty.data_ptr(), ngram.data_ptr(), ban_ids.data_ptr(),
+                                             ban_ids.shape[1], ban_count.data_ptr(), gen_start.data_ptr(),
+                                             presence.data_ptr(), frequency.data_ptr(), bias_count.data_ptr(),
+                                             bias_ids.data_ptr(), bias_vals.data_ptr(), bias_ids.shape[1],
+                                             int(bound), stream_ptr()), "ragk_logits_process_pen")
     return logits
 
 

@@ -246,6 +246,8 @@ def sample_from_logits_candidates(vals, idx, temperature, top_p, u):
 
 LOGITS_PROC_MAX_HIST = 32768  # history entries per row the native kernel stages (csrc/kernels/logits_proc.hip)
 LOGITS_PROC_MAX_NGRAM = 8
+LOGIT_BIAS_MAX = 300  # logit_bias entries per request (the width of the device bias tables)
+PENALTY_GEN_MAX = 8192  # generated tokens a frequency / presence penalty may count (the kernel's LDS table)
 
 
 def hist_write(ids, rows, pos, hist):
@@ -265,6 +267,30 @@ def repetition_penalty_row(x, seq, penalty, vocab_offset=0):
     return x
 
 
+def logit_bias_row(x, ids, vals, vocab_offset=0):
+    """logit_bias on one (shard of a) row, in place: x[id] = x[id] + bias for every (id, bias) whose id lies
+    inside [vocab_offset, vocab_offset + len(x)). The ids are distinct."""
+    t = ids.long() - vocab_offset
+    keep = (t >= 0) & (t < x.numel())
+    x[t[keep]] = x[t[keep]] + vals[keep]
+    return x
+
+
+def frequency_presence_row(x, gen, frequency, presence, vocab_offset=0):
+    """OpenAI's frequency and presence penalties on one (shard of a) row, in place: every distinct id of the
+    GENERATED tokens `gen` with count c gets (x - frequency * float(c)) - presence, three separately rounded
+    fp32 operations (frequency / presence: fp32 scalars)."""
+    t, c = torch.unique(gen.long(), return_counts=True)
+    t = t - vocab_offset
+    keep = (t >= 0) & (t < x.numel())
+    t, c = t[keep], c[keep].to(torch.float32)
+    v = x[t]
+    v -= frequency * c
+    v -= presence
+    x[t] = v
+    return x
+
+
 def ngram_banned(seq, n):
     """transformers' NoRepeatNGramLogitsProcessor: the ids t[j+n-1] of every j in [0, L-n] whose n-1 tokens
     t[j..j+n-2] equal the last n-1 tokens of the sequence (nothing while L + 1 < n)."""
@@ -278,12 +304,24 @@ def ngram_banned(seq, n):
     return win[hit, n - 1].long()
 
 
-def logits_process(logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, ban_ids, ban_count):
+def logits_process(logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, ban_ids, ban_count, *, gen_start=None,
+                   presence=None, frequency=None, bias_ids=None, bias_vals=None, bias_count=None, gen_bound=None):
     """History-dependent logit processors on fp32 logits [B, V] (a vocab shard starting at vocab_offset), in
     place, in transformers' order: repetition penalty, then the -inf writes of the n-gram ban and of the
     min_new_tokens ban list (ban_ids[b, :ban_count[b]]). Row b reads history row rows[b] (< 0: the row is left
-    untouched) of length pos[b] + 1; with `ids` given (decode) hist[rows[b], pos[b]] = ids[b] is stored first."""
+    untouched) of length pos[b] + 1; with `ids` given (decode) hist[rows[b], pos[b]] = ids[b] is stored first.
+
+    The keyword arguments (all None: the chain above, unchanged) add the OpenAI-style controls, all six together:
+    logit_bias FIRST (bias_ids / bias_vals [hist rows, width], indexed by the HISTORY row, bias_count [B] entries
+    of it), then the repetition penalty on the biased values, then frequency [B] and presence [B] over the
+    generated tokens hist[rows[b], gen_start[b] : pos[b] + 1], then the -inf writes, which win. gen_bound: the
+    caller's bound on the generated span of a row with a penalty (default PENALTY_GEN_MAX)."""
     B, V = logits.shape
+    new = (gen_start, presence, frequency, bias_ids, bias_vals, bias_count)
+    pen_form = any(a is not None for a in new)
+    if pen_form:
+        check_penalty_args(B, rows, pos, hist, gen_start, presence, frequency, bias_ids, bias_vals, bias_count,
+                           gen_bound)
     for b in range(B):
         r = int(rows[b])
         if r < 0:
@@ -293,14 +331,56 @@ def logits_process(logits, vocab_offset, ids, rows, pos, hist, penalty, ngram, b
             hist[r, p] = ids[b]
         seq = hist[r, :p + 1]
         x = logits[b]
+        if pen_form and int(bias_count[b]) > 0:
+            nb = int(bias_count[b])
+            logit_bias_row(x, bias_ids[r, :nb], bias_vals[r, :nb], vocab_offset)
         pen = float(penalty[b])
         if pen != 1.0:
             repetition_penalty_row(x, seq, torch.tensor(pen, dtype=torch.float32), vocab_offset)
+        if pen_form and (float(presence[b]) != 0.0 or float(frequency[b]) != 0.0):
+            frequency_presence_row(x, seq[int(gen_start[b]):], frequency[b].clone(), presence[b].clone(), vocab_offset)
         n = int(ngram[b])
         bans = [ngram_banned(seq, n) if n > 0 else seq[:0].long(), ban_ids[b, :int(ban_count[b])].long()]
         t = torch.cat(bans) - vocab_offset
         x[t[(t >= 0) & (t < V)]] = float("-inf")
     return logits
+
+
+def check_penalty_args(B, rows, pos, hist, gen_start, presence, frequency, bias_ids, bias_vals, bias_count, gen_bound,
+                       read_rows=True):
+    """Host-side refusals of the penalty form of logits_process, shared by both backends (ValueError, before any
+    launch): a missing argument, wrong shapes / dtypes, a bias table narrower than a row's bias_count, a gen_bound
+    over PENALTY_GEN_MAX and, with read_rows (the arguments are host tensors), a gen_start outside 0..pos + 1 or
+    a penalised generated span over the bound."""
+    if any(a is None for a in (gen_start, presence, frequency, bias_ids, bias_vals, bias_count)):
+        raise ValueError("gen_start, presence, frequency, bias_ids, bias_vals and bias_count go together")
+    for t, dt, name in ((gen_start, torch.int32, "gen_start"), (bias_count, torch.int32, "bias_count"),
+                        (presence, torch.float32, "presence"), (frequency, torch.float32, "frequency")):
+        if t.dtype != dt or t.dim() != 1 or t.numel() != B or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous %s [%d] tensor" % (name, str(dt).split(".")[1], B))
+    for t, dt, name in ((bias_ids, torch.int32, "bias_ids"), (bias_vals, torch.float32, "bias_vals")):
+        if t.dtype != dt or t.dim() != 2 or t.shape[0] != hist.shape[0] or t.shape[1] < 1 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous %s [history rows = %d, width] tensor"
+                             % (name, str(dt).split(".")[1], hist.shape[0]))
+    if bias_ids.shape != bias_vals.shape:
+        raise ValueError("bias_ids and bias_vals must have one shape")
+    bound = PENALTY_GEN_MAX if gen_bound is None else int(gen_bound)
+    if not 0 <= bound <= PENALTY_GEN_MAX:
+        raise ValueError("a generated span of %d tokens exceeds the %d the penalties count" % (bound, PENALTY_GEN_MAX))
+    if not read_rows:
+        return bound
+    for b in range(B):
+        if int(rows[b]) < 0:
+            continue
+        if not 0 <= int(bias_count[b]) <= bias_ids.shape[1]:
+            raise ValueError("bias_count[%d] = %d does not fit the %d-wide bias table"
+                             % (b, int(bias_count[b]), bias_ids.shape[1]))
+        g, p = int(gen_start[b]), int(pos[b])
+        if not 0 <= g <= p + 1:
+            raise ValueError("gen_start[%d] = %d outside 0..pos + 1 = %d" % (b, g, p + 1))
+        if (float(presence[b]) != 0.0 or float(frequency[b]) != 0.0) and p + 1 - g > bound:
+            raise ValueError("row %d: a generated span of %d tokens exceeds the bound %d" % (b, p + 1 - g, bound))
+    return bound
 
 
 LOGPROBS_MAX = 20  # alternatives per generated position (csrc/kernels/logprobs.hip LP_MAX)

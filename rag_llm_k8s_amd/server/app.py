@@ -16,6 +16,11 @@ New (documents can be listed, removed, replaced and filtered on; the reference c
   POST /generate     optional "repetition_penalty": float > 0, "no_repeat_ngram_size": 0..8, "min_new_tokens":
                      0..MAX_NEW_TOKENS -> override REPETITION_PENALTY / NO_REPEAT_NGRAM_SIZE / MIN_NEW_TOKENS for
                      this request (transformers' generate() semantics); a refused value -> 400 {"error"}
+  POST /generate     optional "presence_penalty", "frequency_penalty": numbers in -2..2 (OpenAI's semantics: every
+                     token GENERATED so far loses frequency * its count + presence; prompt tokens do not count),
+                     "logit_bias": {"<token id>": number in -100..100, ...} (at most 300 entries, added to those
+                     tokens' logits before everything else) -> override PRESENCE_PENALTY / FREQUENCY_PENALTY /
+                     LOGIT_BIAS for this request; a refused value or a non-integer key -> 400 {"error"}
   POST /generate     optional "logprobs": N (integer 0..20; overrides LOGPROBS) -> the response gains "logprobs":
                      {"token_ids", "tokens", "token_logprobs", "top_logprobs": [[{"id", "token", "logprob"}, ...],
                      ...], "mean_logprob"} over every generated token (a final eos included): log_softmax of the

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import dataclasses
 import faulthandler
+import json
 import logging
 import os
 import queue
@@ -25,7 +26,7 @@ import time
 import numpy as np
 import torch
 
-from ..engine.llm_engine import SamplingParams
+from ..engine.llm_engine import SamplingParams, normalize_logit_bias
 from ..ingest import pdf as pdfmod
 from ..ingest.text import NO_RESULTS, build_context, build_prompt, chunk_metadata, postprocess, split_text
 from ..utils import faults, metrics
@@ -284,7 +285,10 @@ class RagService:
                                      repetition_penalty=float(getattr(cfg, "repetition_penalty", 1.0)),
                                      no_repeat_ngram_size=int(getattr(cfg, "no_repeat_ngram_size", 0)),
                                      min_new_tokens=int(getattr(cfg, "min_new_tokens", 0)),
-                                     logprobs=getattr(cfg, "logprobs", None))
+                                     logprobs=getattr(cfg, "logprobs", None),
+                                     presence_penalty=float(getattr(cfg, "presence_penalty", 0.0)),
+                                     frequency_penalty=float(getattr(cfg, "frequency_penalty", 0.0)),
+                                     logit_bias=self.config_logit_bias(getattr(cfg, "logit_bias", "")))
         llm_engine.check_params(self.params)
         self.loop = EngineLoop(llm_engine, control=control)
         # tensor-parallel group (set by the TP server): PDF ingest is data-parallel over it and, with
@@ -428,8 +432,37 @@ class RagService:
 
     # per-request sampling fields of /generate (JSON names = SamplingParams names) and their JSON types: the
     # logit processors, and "logprobs": N (0..20) for per-token log-probabilities with N alternatives
+    # "presence_penalty" / "frequency_penalty" (numbers in -2..2) and "logit_bias": {"<token id>": number}
     REQUEST_PARAM_FIELDS = {"repetition_penalty": (int, float), "no_repeat_ngram_size": (int,),
-                            "min_new_tokens": (int,), "logprobs": (int,)}
+                            "min_new_tokens": (int,), "logprobs": (int,), "presence_penalty": (int, float),
+                            "frequency_penalty": (int, float), "logit_bias": (dict,)}
+
+    @staticmethod
+    def parse_logit_bias(obj):
+        """SamplingParams.logit_bias from a JSON object {"<token id>": number}: the keys are decimal integer
+        strings (JSON has no integer keys), the values numbers (not bools). Ranges, the vocabulary and the entry
+        count are the engine's admission checks."""
+        if not isinstance(obj, dict):
+            raise ValueError("logit_bias must be an object {\"<token id>\": number} (got %r)" % (obj,))
+        pairs = []
+        for k, v in obj.items():
+            if not isinstance(k, str) or not k.isascii() or not k.isdigit():
+                raise ValueError("logit_bias: key %r is not a decimal token id" % (k,))
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise ValueError("logit_bias: the bias of token %s must be a number (got %r)" % (k, v))
+            pairs.append((int(k), float(v)))
+        return normalize_logit_bias(pairs)
+
+    @classmethod
+    def config_logit_bias(cls, text):
+        """The LOGIT_BIAS default: a JSON object string ("" = none)."""
+        if not text or not str(text).strip():
+            return ()
+        try:
+            obj = json.loads(text)
+        except ValueError as e:
+            raise ValueError("LOGIT_BIAS is not a JSON object: %s" % e)
+        return cls.parse_logit_bias(obj)
 
     def logprobs_object(self, s):
         """The "logprobs" object of a response (None for a request that did not ask): every generated token of
@@ -445,13 +478,16 @@ class RagService:
                 "top_logprobs": top, "mean_logprob": (sum(s.logprobs) / n) if n else None}
 
     def request_params(self, overrides):
-        """The service's default SamplingParams with a request's logit-processor fields replaced. Raises
+        """The service's default SamplingParams with a request's sampling fields replaced. Raises
         ValueError (the route's 400) for a field of the wrong JSON type or a value the engine refuses."""
         kw = {}
         for k, v in overrides.items():
             types = self.REQUEST_PARAM_FIELDS.get(k)
             if types is None:
                 raise ValueError("unknown sampling field %r" % (k,))
+            if dict in types:  # the object-typed field
+                kw[k] = self.parse_logit_bias(v)
+                continue
             if isinstance(v, bool) or not isinstance(v, types):
                 raise ValueError("%s must be %s (got %r)" % (k, "a number" if float in types else "an integer", v))
             kw[k] = float(v) if float in types else v

@@ -5,7 +5,14 @@ and all three processors on (repetition penalty 1.3, 3-gram ban, 3 banned stop i
 kernel stores the step's id first). Chunking as the engine picks it (llm_engine.SMALL_BATCH_TOPK_*). Each figure
 is the median of 5 x 5 replays of a hipGraph that holds 20 copies of the sequence. The processor runs in place,
 so the penalised logits shrink from replay to replay; its work does not depend on their values. Prints one JSON
-line per batch size."""
+line per batch size.
+
+--penalties: the penalty form of the launch (ragk_logits_process_pen: logit_bias, frequency and presence penalties
+on top of the three processors above, all six on) alone in a graph, against the old launch alone on the same
+history, at B = 1 and B = 32: 5200-token prompts followed by a generated span of 150 or 8192 tokens (ids drawn
+from the whole vocabulary, so nearly all distinct: the counting table at its fullest), with 0 and with 300 bias
+entries. One JSON line per (batch, span, bias entries)."""
+import argparse
 import json
 import os
 import sys
@@ -16,6 +23,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from rag_llm_k8s_amd.ops import native as N  # noqa: E402
 
 V, K, HIST, MAX_LEN, BAN_W = 128256, 64, 5200, 16384, 16
+BIAS_W = 300
 
 
 def timed(fn, iters=5, reps=5):
@@ -45,6 +53,45 @@ def graph_of(fn, copies=20):
             fn()
     torch.cuda.current_stream().wait_stream(st)
     return g
+
+
+def penalties():
+    dev = "cuda"
+    for B in (1, 32):
+        g = torch.Generator(device=dev).manual_seed(B)
+        logits = torch.randn(B, V, device=dev, generator=g) * 3
+        hist = torch.randint(0, V, (B, MAX_LEN), device=dev, generator=g, dtype=torch.int32)
+        rows = torch.arange(B, dtype=torch.int32, device=dev)
+        ids = torch.randint(0, V, (B,), device=dev, generator=g, dtype=torch.int32)
+        pen = torch.full((B,), 1.3, device=dev)
+        ng = torch.full((B,), 3, dtype=torch.int32, device=dev)
+        ban_ids = torch.zeros((B, BAN_W), dtype=torch.int32, device=dev)
+        ban_ids[:, :3] = torch.tensor([128001, 128008, 128009], dtype=torch.int32, device=dev)
+        ban_count = torch.full((B,), 3, dtype=torch.int32, device=dev)
+        gen_start = torch.full((B,), HIST, dtype=torch.int32, device=dev)
+        pres = torch.full((B,), 0.5, device=dev)
+        freq = torch.full((B,), 0.25, device=dev)
+        bias_ids = torch.stack([torch.randperm(V, device=dev, generator=g)[:BIAS_W] for _ in range(B)]).int()
+        bias_vals = torch.rand(B, BIAS_W, device=dev, generator=g) * 2 - 1
+        for span in (150, 8192):
+            pos = torch.full((B,), HIST + span - 1, dtype=torch.int32, device=dev)
+
+            def old():
+                N.logits_process(logits, 0, ids, rows, pos, hist, pen, ng, ban_ids, ban_count)
+
+            t_old = timed(graph_of(old).replay) / 20
+            for nbias in (0, BIAS_W):
+                bias_count = torch.full((B,), nbias, dtype=torch.int32, device=dev)
+
+                def new():
+                    N.logits_process(logits, 0, ids, rows, pos, hist, pen, ng, ban_ids, ban_count,
+                                     gen_start=gen_start, presence=pres, frequency=freq, bias_ids=bias_ids,
+                                     bias_vals=bias_vals, bias_count=bias_count, gen_bound=span)
+
+                t_new = timed(graph_of(new).replay) / 20
+                print(json.dumps({"B": B, "V": V, "prompt": HIST, "span": span, "bias": nbias,
+                                  "old_alone_dev_us": round(t_old, 2), "pen_alone_dev_us": round(t_new, 2),
+                                  "added_us": round(t_new - t_old, 2)}), flush=True)
 
 
 def main():
@@ -90,4 +137,6 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--penalties", action="store_true", help="measure the penalty form of the launch instead")
+    penalties() if ap.parse_args().penalties else main()
