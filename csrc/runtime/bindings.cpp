@@ -3,6 +3,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include "lexical.h"
 #include "runtime.h"
 #include "tokenizer.h"
 
@@ -78,6 +79,27 @@ PYBIND11_MODULE(_ragk_rt, m) {
     if (x.ndim() != 2) throw std::invalid_argument("xb must be [n, d]");
     write_flat_index(path, x.data(), x.shape(0), (int32_t)x.shape(1));
   });
+
+  // lexical analyzer (lexical.h): a batch of UTF-8 texts (str or bytes) -> CSR (row_ptr int64 [n + 1],
+  // terms uint32, tf uint16, doc_len int32 [n]); the GIL is released while the texts are analysed
+  m.def("lex_analyze_batch", [](const std::vector<std::string>& texts) {
+    LexCsr r;
+    {
+      py::gil_scoped_release nogil;
+      r = lex_analyze_batch(texts);
+    }
+    return py::make_tuple(py::array_t<int64_t>(r.row_ptr.size(), r.row_ptr.data()),
+                          py::array_t<uint32_t>(r.terms.size(), r.terms.data()),
+                          py::array_t<uint16_t>(r.tf.size(), r.tf.data()),
+                          py::array_t<int32_t>(r.doc_len.size(), r.doc_len.data()));
+  });
+  // term ids of one text's tokens in order of appearance (queries)
+  m.def("lex_tokens", [](const std::string& text) {
+    std::vector<uint32_t> t;
+    lex_tokens(text, t);
+    return py::array_t<uint32_t>(t.size(), t.data());
+  });
+  m.def("lex_remap", [](uint32_t h) { return lex_remap(h); });
 
   py::class_<BlockManager>(m, "BlockManager")
       .def(py::init<int, bool>(), py::arg("num_blocks"), py::arg("reserve_scratch") = true)

@@ -92,6 +92,14 @@ class RagConfig:
     rerank_candidates: int = 32  # retrieve_k <= N <= 64 (the width of the search kernels' top lists)
     rerank_max_len: int = 512  # tokens per (query, chunk) pair; capped by the model's positions
     rerank_batch_tokens: int = 65536
+    # hybrid retrieval (opt-in): a BM25 index over the chunk texts next to the dense one; both are searched
+    # hybrid_candidates deep and the two lists fused by reciprocal rank (index/lexical.py). A /generate request may
+    # switch it per query with "hybrid": true | false
+    hybrid_search: str = "off"  # off | rrf
+    hybrid_candidates: int = 32  # max(retrieve_k, rerank_candidates) <= N <= 64
+    bm25_k1: float = 1.2  # >= 0
+    bm25_b: float = 0.75  # 0..1
+    rrf_k: float = 60.0  # > 0
     extra: dict = field(default_factory=dict)
 
     @classmethod
@@ -120,6 +128,8 @@ class RagConfig:
             "INDEX_SHARDED": ("index_sharded", bool), "KV_CACHE_DTYPE": ("kv_cache_dtype", str),
             "RERANK_MODEL": ("rerank_model", str), "RERANK_CANDIDATES": ("rerank_candidates", int),
             "RERANK_MAX_LEN": ("rerank_max_len", int), "RERANK_BATCH_TOKENS": ("rerank_batch_tokens", int),
+            "HYBRID_SEARCH": ("hybrid_search", str), "HYBRID_CANDIDATES": ("hybrid_candidates", int),
+            "BM25_K1": ("bm25_k1", float), "BM25_B": ("bm25_b", float), "RRF_K": ("rrf_k", float),
         }
         for env, (attr, cast) in m.items():
             setattr(c, attr, _env(env, getattr(c, attr), cast))
@@ -134,6 +144,7 @@ class RagConfig:
         if c.kv_cache_dtype not in ("bf16", "fp8"):
             raise ValueError("KV_CACHE_DTYPE must be bf16 or fp8, got %r" % c.kv_cache_dtype)
         c.validate_rerank()
+        c.validate_hybrid()
         return c
 
     RERANK_MAX_CANDIDATES = 64
@@ -147,6 +158,37 @@ class RagConfig:
                              % (self.RERANK_MAX_CANDIDATES, self.retrieve_k, self.rerank_candidates))
         if self.rerank_max_len < 8 or self.rerank_batch_tokens < self.rerank_max_len:
             raise ValueError("RERANK_MAX_LEN must be >= 8 and RERANK_BATCH_TOKENS >= RERANK_MAX_LEN")
+
+    HYBRID_MAX_CANDIDATES = 64
+
+    @property
+    def hybrid(self) -> bool:
+        return str(self.hybrid_search).strip().lower() == "rrf"
+
+    def validate_hybrid(self):
+        """HYBRID_SEARCH is off (or empty) or rrf; with it on, the candidate depth must cover what the later
+        stages take (retrieve_k, and rerank_candidates with a reranker) and fit the kernels' lists, and the index
+        must not be row-sharded."""
+        mode = str(self.hybrid_search or "").strip().lower() or "off"
+        if mode not in ("off", "rrf"):
+            raise ValueError("HYBRID_SEARCH must be off or rrf, got %r" % self.hybrid_search)
+        self.hybrid_search = mode
+        if mode == "off":
+            return
+        lo = max(self.retrieve_k, self.rerank_candidates)
+        if not lo <= self.hybrid_candidates <= self.HYBRID_MAX_CANDIDATES:
+            raise ValueError("HYBRID_CANDIDATES must be in %d..%d (max(RETRIEVE_K, RERANK_CANDIDATES) .. the width "
+                             "of the search kernels' lists), got %d" % (lo, self.HYBRID_MAX_CANDIDATES,
+                                                                         self.hybrid_candidates))
+        if not self.bm25_k1 >= 0:
+            raise ValueError("BM25_K1 must be >= 0, got %r" % self.bm25_k1)
+        if not 0 <= self.bm25_b <= 1:
+            raise ValueError("BM25_B must be in 0..1, got %r" % self.bm25_b)
+        if not self.rrf_k > 0:
+            raise ValueError("RRF_K must be > 0, got %r" % self.rrf_k)
+        if self.index_sharded:
+            raise ValueError("HYBRID_SEARCH=rrf is not supported on a row-sharded index (INDEX_SHARDED): the "
+                             "lexical index is not sharded")
 
     def resolved_device(self) -> str:
         if self.device != "auto":

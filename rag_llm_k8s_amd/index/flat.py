@@ -74,6 +74,12 @@ def mask_allowed(masks, qmask, ids) -> np.ndarray:
     return out
 
 
+def pair_sqdist(x, q) -> torch.Tensor:
+    """fp32 sum((x[j] - q[j]) ** 2) per row (the indexes' distances())."""
+    df = x.float() - q.float()
+    return (df * df).sum(1)
+
+
 COMPACT_PIECE_FLOATS = 4 << 20  # FlatL2Index.compact on the device moves rows in pieces of <= 16 MB
 
 
@@ -203,6 +209,24 @@ class FlatL2Index:
         D[:, :kk] = dv[:, :kk]
         I[:, :kk] = di[:, :kk]
         return D, I
+
+    def distances(self, q, ids):
+        """Squared L2 between query row q[j] and stored vector ids[j], pairwise: q [m, d], ids [m] (each in
+        [0, ntotal)) -> fp32 [m] on the host. The rows are gathered (l2_gather on the GPU) and the squares
+        summed by torch in fp32 -- the distance of a chunk that entered a result list by another route."""
+        q = torch.as_tensor(q).reshape(-1, self.d).float()
+        ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+        if len(ids) != q.shape[0]:
+            raise ValueError("distances: one id per query row")
+        with self._lock:
+            if len(ids) and (ids.min() < 0 or ids.max() >= self.ntotal):
+                raise ValueError("distances: ids within [0, ntotal)")
+            if len(ids) == 0:
+                return torch.zeros(0)
+            if self._n is not None:
+                x = self._n.l2_gather(self._xt, self._cap, torch.from_numpy(ids.astype(np.int32)).to(self.device))
+                return pair_sqdist(x, q.to(self.device)).cpu()
+            return pair_sqdist(self._xb[torch.from_numpy(ids)], q)
 
     def reconstruct_all(self) -> np.ndarray:
         with self._lock:

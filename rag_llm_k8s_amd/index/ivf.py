@@ -276,6 +276,33 @@ class IVFFlatIndex:
             I[qi, :kk] = ids[order[:kk]]
         return D, I
 
+    def distances(self, q, ids):
+        """Squared L2 between query row q[j] and the vector with id ids[j], pairwise (FlatL2Index.distances):
+        the rows are found by their original id, gathered and the squares summed by torch in fp32."""
+        from .flat import pair_sqdist
+
+        q = torch.as_tensor(q).reshape(-1, self.d).float()
+        ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+        if len(ids) != q.shape[0]:
+            raise ValueError("distances: one id per query row")
+        with self._lock:
+            if len(ids) and (ids.min() < 0 or ids.max() >= self.ntotal):
+                raise ValueError("distances: ids within [0, ntotal)")
+            if len(ids) == 0:
+                return torch.zeros(0)
+            if self.device.type == "cuda":
+                from ..ops import native
+
+                rows = torch.nonzero(self._ids_dev >= 0).reshape(-1)
+                row_of = torch.empty(self.ntotal, dtype=torch.int32, device=self.device)
+                row_of[self._ids_dev[rows].long()] = rows.int()
+                idx = row_of[torch.from_numpy(ids).to(self.device)].contiguous()
+                return pair_sqdist(native.l2_gather(self._xt, self._cap, idx), q.to(self.device)).cpu()
+            all_ids = np.concatenate(self.ids)
+            order = np.argsort(all_ids, kind="stable")  # ids are a permutation of [0, ntotal)
+            x = np.concatenate(self.lists)[order[ids]]
+            return pair_sqdist(torch.from_numpy(x), q)
+
     def compact(self, keep):
         """Drop every vector whose id is not in `keep` (sorted ids); new id = rank among the kept. Centroids
         and list assignment stay: the index equals one with these centroids to which the kept vectors were

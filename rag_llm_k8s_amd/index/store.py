@@ -22,6 +22,7 @@ Reference behaviour and its fixes:
 """
 from __future__ import annotations
 
+import contextlib
 import logging
 import os
 import threading
@@ -38,13 +39,26 @@ log = logging.getLogger(__name__)
 
 class DocumentStore:
     def __init__(self, index_path, dim, device="cpu", index_type="flat", ivf_nlist=1024, ivf_nprobe=32,
-                 recovery="rebuild", shard=None):
-        """shard = (group, rank, world): INDEX_SHARDED tensor-parallel mode -- this rank keeps the rows
+                 recovery="rebuild", shard=None, lexical=False, hybrid_candidates=32, bm25_k1=1.2, bm25_b=0.75,
+                 rrf_k=60.0):
+        """lexical=True: the store also owns a LexicalIndex (index/lexical.py, BM25 over the chunk texts, row i =
+        metadata entry i) kept in step with the dense index under _wlock; search(texts=...) then fuses the two
+        result lists by reciprocal rank (hybrid_candidates deep each, BM25 k1 / b, fusion constant rrf_k). It is
+        not persisted: load() rebuilds it from the metadata texts.
+        shard = (group, rank, world): INDEX_SHARDED tensor-parallel mode -- this rank keeps the rows
         g % world == rank of the index (parallel/dp.py ShardedFlatIndex) in `<index_path>.shard<r>of<W>`
         (a faiss IxF2 file of its rows); every rank keeps the full metadata list, rank 0 persists it.
         search() is then a collective (all ranks call it together, followers with no queries)."""
         self.sharded = shard is not None
         self.shard = shard
+        if lexical and self.sharded:
+            raise ValueError(self.SHARDED_REFUSAL % "hybrid (lexical) search")
+        if lexical and not 1 <= int(hybrid_candidates) <= 64:
+            raise ValueError("hybrid_candidates must be in 1..64 (the width of the search kernels' top lists)")
+        if lexical and not (float(bm25_k1) >= 0 and 0 <= float(bm25_b) <= 1 and float(rrf_k) > 0):
+            raise ValueError("hybrid search needs bm25_k1 >= 0, 0 <= bm25_b <= 1 and rrf_k > 0")
+        self.hybrid_candidates = int(hybrid_candidates)
+        self.bm25_k1, self.bm25_b, self.rrf_k = float(bm25_k1), float(bm25_b), float(rrf_k)
         self.index_path = index_path
         self.index_file = index_path if shard is None else "%s.shard%dof%d" % (index_path, shard[1], shard[2])
         self.persist_meta = shard is None or shard[1] == 0
@@ -55,6 +69,7 @@ class DocumentStore:
         self.index_type = index_type
         self.ivf_nlist, self.ivf_nprobe = ivf_nlist, ivf_nprobe
         self.index = self._new_index()
+        self.lexical = self._new_lexical() if lexical else None
         self.metadata = []
         self._keys = set()
         self._wlock = threading.RLock()
@@ -85,6 +100,15 @@ class DocumentStore:
             return IVFFlatIndex(self.dim, device=self.device, nlist=self.ivf_nlist, nprobe=self.ivf_nprobe)
         return FlatL2Index(self.dim, device=self.device)
 
+    def _new_lexical(self, meta=()):
+        """A LexicalIndex of the metadata entries' texts (an entry without one is an empty document)."""
+        from .lexical import LexicalIndex, doc_text
+
+        lex = LexicalIndex(device=self.device)
+        if len(meta):
+            lex.add([doc_text(m) for m in meta])
+        return lex
+
     # ------------------------------------------------------------------ lifecycle
     def ensure_exists(self):
         """Reference ensure_index_exists(): create an empty index + [] metadata if missing."""
@@ -111,6 +135,8 @@ class DocumentStore:
                 os.replace(p, p + tag)
         log.error("index %s unreadable (%s); moved aside as *%s, starting empty", self.index_file, err, tag)
         self.index = self._new_index()
+        if self.lexical is not None:
+            self.lexical = self._new_lexical()
         self.metadata = []
         self._keys = set()
         self._reset_live()
@@ -150,7 +176,9 @@ class DocumentStore:
             from .ivf import IVFFlatIndex
 
             idx = IVFFlatIndex.from_lists(r, device=self.device)
+        lex = self._new_lexical(meta) if self.lexical is not None else None  # not persisted: rebuilt from the texts
         self.index = idx
+        self.lexical = lex
         self.metadata = list(meta)
         self._keys = {(m.get("filename"), m.get("chunk_id")) for m in self.metadata if isinstance(m, dict)}
         self._reset_live()
@@ -184,6 +212,8 @@ class DocumentStore:
             return
         keep = np.nonzero(self._live)[0]
         self.index.compact(keep)
+        if self.lexical is not None:
+            self.lexical.compact(keep)
         self.metadata = [self.metadata[i] for i in keep.tolist()]  # a new list: searches in flight keep theirs
         self._reset_live()
         metrics.inc("index_compactions")
@@ -289,6 +319,10 @@ class DocumentStore:
                 if self.index_type == "ivf" and not self.index.is_trained:
                     self.index.train(vecs[keep])
                 self.index.add(vecs[keep])
+                if self.lexical is not None:
+                    from .lexical import doc_text
+
+                    self.lexical.add([doc_text(metadata[i]) for i in keep])
                 for i in keep:
                     self.metadata.append(metadata[i])
                     self._keys.add((metadata[i]["filename"], metadata[i]["chunk_id"]))
@@ -383,10 +417,15 @@ class DocumentStore:
             qmask[j] = row_of[key]
         return pack_masks(np.stack(rows)), qmask
 
-    def search(self, qvecs, k, filters=None):
+    def search(self, qvecs, k, filters=None, texts=None, trace=None):
         """Batched search -> list (per query) of [(metadata, squared_l2)] ascending, -1 dropped.
         filters: per query None or a collection of filenames the results must come from (a filter naming
-        no known document yields no results for that query)."""
+        no known document yields no results for that query).
+        texts (a store with lexical=True): per query its text, or None for a query that stays dense-only. A
+        query with a text gets the hybrid result (_search_hybrid); the others are searched exactly as without
+        `texts`, in a call of their own. trace (utils.metrics.Trace): receives the spans "lexical" and "fuse"."""
+        if texts is not None and any(t is not None for t in texts):
+            return self._search_mixed(qvecs, k, filters, list(texts), trace)
         if self.sharded and filters is not None and any(f is not None for f in filters):
             raise ValueError(self.SHARDED_REFUSAL % "filtering")
         with self._wlock:  # consistent (index, metadata) pair: an append cannot land in between
@@ -404,6 +443,85 @@ class DocumentStore:
             for d, i in zip(drow, irow):
                 if 0 <= i < n:
                     res.append((meta[i], float(d)))
+            out.append(res)
+        return out
+
+    def _search_mixed(self, qvecs, k, filters, texts, trace=None):
+        """search() of a batch in which some queries carry a text: those go through _search_hybrid together,
+        the rest through the plain search together; the results return in the batch's order."""
+        if self.lexical is None:
+            raise ValueError("hybrid search needs a store built with lexical=True")
+        import torch
+
+        q = torch.as_tensor(np.asarray(qvecs.cpu() if hasattr(qvecs, "cpu") else qvecs, dtype=np.float32))
+        q = q.reshape(-1, self.dim)
+        if len(texts) != q.shape[0]:
+            raise ValueError("texts: one entry (a string or None) per query")
+        filters = list(filters) if filters is not None else [None] * len(texts)
+        if len(filters) != len(texts):
+            raise ValueError("filters: one entry (None or filenames) per query")
+        hyb = [i for i, t in enumerate(texts) if t is not None]
+        rest = [i for i, t in enumerate(texts) if t is None]
+        out = [None] * len(texts)
+        for i, r in zip(hyb, self._search_hybrid(q[hyb], k, [filters[i] for i in hyb], [texts[i] for i in hyb],
+                                                    trace)):
+            out[i] = r
+        if rest:
+            fr = [filters[i] for i in rest]
+            for i, r in zip(rest, self.search(q[rest], k, filters=fr if any(f is not None for f in fr) else None)):
+                out[i] = r
+        return out
+
+    def _search_hybrid(self, q, k, filters, texts, trace=None):
+        """Dense search and BM25 search, both hybrid_candidates deep and under the same per-query masks, fused by
+        reciprocal rank: fused(d) = sum over the lists holding d of 1 / (rrf_k + rank), ordered by fused
+        descending then id ascending, cut to k. The tuples stay (metadata, squared_l2): a chunk of the dense list
+        keeps the distance the search returned, a lexical-only chunk gets index.distances(). The metadata dicts
+        are copies that also carry dense_rank / lexical_rank (1-based, None = not in that list) and
+        lexical_score (None likewise)."""
+        from .lexical import rrf_fuse
+
+        span = trace.span if trace is not None else (lambda stage: contextlib.nullcontext())
+        depth = self.hybrid_candidates
+        nq = q.shape[0]
+        with self._wlock:
+            masks, qmask = self._filter_masks(filters, nq)
+            if masks is None:
+                D, I = self.index.search(q, depth)
+            else:
+                D, I = self.index.search(q, depth, masks=masks, qmask=qmask)
+            live = self._live if self._dead else None
+            with span("lexical"):
+                S, L = self.lexical.search(texts, depth, k1=self.bm25_k1, b=self.bm25_b, masks=masks, qmask=qmask,
+                                           live=live)
+            with span("fuse"):
+                meta = self.metadata
+                n = len(meta)
+                D, I, S, L = D.tolist(), I.tolist(), S.tolist(), L.tolist()
+                picked, need_q, need_id = [], [], []
+                for j in range(nq):
+                    dense = {i: (r + 1, d) for r, (d, i) in enumerate((d, i) for d, i in zip(D[j], I[j]) if 0 <= i < n)}
+                    lex = {i: (r + 1, s) for r, (s, i) in enumerate((s, i) for s, i in zip(S[j], L[j]) if 0 <= i < n)}
+                    rows = []
+                    for i, _ in rrf_fuse([list(dense), list(lex)], self.rrf_k, k):
+                        if i not in dense:
+                            need_q.append(j)
+                            need_id.append(i)
+                        rows.append((i, dense.get(i), lex.get(i)))
+                    picked.append(rows)
+                extra = {}
+                if need_id:  # lexical-only chunks: their real distance, one gather for the whole batch
+                    dist = self.index.distances(q[need_q], need_id).tolist()
+                    extra = {(j, i): d for j, i, d in zip(need_q, need_id, dist)}
+        out = []
+        for j, rows in enumerate(picked):
+            res = []
+            for i, de, le in rows:
+                m = dict(meta[i]) if isinstance(meta[i], dict) else {"text": ""}
+                m["dense_rank"] = de[0] if de else None
+                m["lexical_rank"] = le[0] if le else None
+                m["lexical_score"] = float(le[1]) if le else None
+                res.append((m, float(de[1]) if de else float(extra[(j, i)])))
             out.append(res)
         return out
 

@@ -98,6 +98,11 @@ _SIGS = {
     "ragk_l2_scatter": [P, I, I, P, P, I, S],
     "ragk_l2_append": [P, I, I, I, P, I, S],
     "ragk_l2_gather": [P, I, I, P, I, P, S],
+    # csrc/kernels/lexical.hip (BM25 lexical search over a doc-major CSR)
+    "ragk_lex_max_terms": [],
+    "ragk_lex_search_groups": [I],
+    "ragk_lex_df": [P, P, I, P, I, P, I, P, S],
+    "ragk_lex_search": [P, P, P, P, I, P, P, P, I, I, F, F, F, F, I, P, I, I, P, P, P, P, P, S],
     "ragk_gemm_stream": [P, I, P, I, P, P, I, P, P, I, I, I, I, I, I, I, P, P, S],
     "ragk_gemm_stream_splits": [I, I, I, I],
     "ragk_quant_fp8_rows": [P, I, P, I, P, I, I, S],

@@ -246,6 +246,15 @@ class TorchBackend:
             raise ValueError("rerank_select: need 1 <= k <= N <= %d" % R.SELECT_MAX_N)
         return R.rerank_select(scores, cand_ids, cand_dist, n_valid, k)
 
+    # BM25 lexical search over a doc-major CSR (index/lexical.py) ----------------------------------
+    def lex_df(self, row_ptr, terms, n, qterms, live=None):
+        return R.lex_df(row_ptr, terms, n, qterms, live=live)
+
+    def lex_search(self, row_ptr, terms, tf, doc_len, n, qterms, idf, member, nq, k1, k1p1, b, avgdl, k, masks=None,
+                   qmask=None):
+        return R.lex_search(row_ptr, terms, tf, doc_len, n, qterms, idf, member, nq, k1, k1p1, b, avgdl, k,
+                            masks=masks, qmask=qmask)
+
     # sampling -----------------------------------------------------------------
     def topk_candidates(self, logits, K, vocab_offset=0, max_cand=512, chunks=None):
         k = min(K, logits.shape[1])
@@ -433,6 +442,18 @@ class NativeBackend(TorchBackend):
 
     def rerank_select(self, scores, cand_ids, cand_dist, n_valid, k):
         return self.n.rerank_select(scores, cand_ids, cand_dist, n_valid, k)
+
+    def lex_df(self, row_ptr, terms, n, qterms, live=None):
+        if live is not None and not live.is_cuda:
+            live = live.to(row_ptr.device)
+        return self.n.lex_df(row_ptr, terms, n, qterms, live=live)
+
+    def lex_search(self, row_ptr, terms, tf, doc_len, n, qterms, idf, member, nq, k1, k1p1, b, avgdl, k, masks=None,
+                   qmask=None):
+        if masks is not None and not masks.is_cuda:
+            masks = masks.to(row_ptr.device)
+        return self.n.lex_search(row_ptr, terms, tf, doc_len, n, qterms, idf, member, nq, k1, k1p1, b, avgdl, k,
+                                 masks=masks, qmask=qmask)
 
     def topk_candidates(self, logits, K, vocab_offset=0, max_cand=512, chunks=None):
         return self.n.topk_candidates(logits, K, vocab_offset=vocab_offset, max_cand=max_cand, chunks=chunks)

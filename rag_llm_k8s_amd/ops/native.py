@@ -1727,3 +1727,88 @@ def l2_gather(xt, cap, idx, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- BM25 lexical search
+from .reference import LEX_MAX_QUERIES, LEX_MAX_TERMS  # noqa: E402  (one definition, both backends)
+
+
+def _lex_csr(row_ptr, terms, n, tf=None, doc_len=None):
+    _req(row_ptr.is_cuda and row_ptr.dtype == torch.int64 and row_ptr.dim() == 1 and row_ptr.is_contiguous()
+         and 0 <= n < row_ptr.numel() and n < 2 ** 31, "row_ptr int64 [>= n + 1] on the GPU")
+    dev = row_ptr.device
+    _req(terms.dtype == torch.int32 and terms.dim() == 1 and terms.is_contiguous() and terms.device == dev,
+         "terms int32 (uint32 bit patterns) on the launch device")
+    if tf is not None:
+        _req(tf.dtype == torch.int16 and tf.dim() == 1 and tf.is_contiguous() and tf.device == dev
+             and tf.numel() == terms.numel(), "tf int16 (uint16 bit patterns), one per entry")
+        _req(doc_len.dtype == torch.int32 and doc_len.dim() == 1 and doc_len.is_contiguous() and doc_len.device == dev
+             and doc_len.numel() >= n, "doc_len int32 [>= n]")
+    return dev
+
+
+def _lex_table(qterms, dev):
+    """The launch's term table: int32 [T] (uint32 bit patterns), T <= 4096, strictly ascending as unsigned ids.
+    A host tensor is checked without a device sync and uploaded; a device tensor is checked with one."""
+    _req(qterms.dtype == torch.int32 and qterms.dim() == 1 and qterms.is_contiguous(), "qterms int32 [T]")
+    T = qterms.numel()
+    _req(T <= LEX_MAX_TERMS, "at most %d terms per launch" % LEX_MAX_TERMS)
+    if T > 1:
+        u = qterms.long() & 0xFFFFFFFF
+        _req(bool((u[1:] > u[:-1]).all()), "the term table must be strictly ascending (as unsigned ids)")
+    return qterms if qterms.is_cuda else qterms.to(dev)
+
+
+def lex_df(row_ptr, terms, n, qterms, live=None, live_bits=None, out=None):
+    """int32 [T] on the device: how many of the first n documents of the CSR -- those whose bit is set in the
+    bitmap row `live` (int32 / uint32 words on the device, covering live_bits ids, default all its bits), or
+    all of them -- hold each term of the table (csrc/kernels/lexical.hip lex_df: integer atomics only)."""
+    dev = _lex_csr(row_ptr, terms, n)
+    qt = _lex_table(qterms, dev)
+    T = qt.numel()
+    bits = 0
+    if live is not None:
+        _req(live.is_cuda and live.device == dev and live.is_contiguous() and live.dim() == 1
+             and live.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)), "live int32 [words]")
+        bits = 32 * live.numel() if live_bits is None else int(live_bits)
+        _req(0 <= bits <= 32 * live.numel(), "live_bits within the bitmap row")
+    df = torch.empty(T, dtype=torch.int32, device=dev) if out is None else out
+    _req(df.dtype == torch.int32 and df.device == dev and df.is_contiguous() and tuple(df.shape) == (T,),
+         "out int32 [T]")
+    if T:
+        check(_lib.lib().ragk_lex_df(row_ptr.data_ptr(), terms.data_ptr(), n, qt.data_ptr(), T, ptr(live), bits,
+                                     df.data_ptr(), stream_ptr()), "ragk_lex_df")
+    return df
+
+
+def lex_search(row_ptr, terms, tf, doc_len, n, qterms, idf, member, nq, k1, k1p1, b, avgdl, k, masks=None,
+               qmask=None, mask_bits=None, out=None):
+    """BM25 top-k of up to 64 queries over the first n documents of a doc-major CSR (csrc/kernels/lexical.hip):
+    -> (scores fp32 [nq, k] descending, ids int64 [nq, k], ties -> lower id, padding (0, -1)). qterms / idf /
+    member: the launch's term table (see _lex_table), fp32 idf [T] and int64 membership words [T] (bit q: query
+    q holds the term); host tensors are uploaded. masks / qmask: per-query id bitmaps (see _mask_args). out: optional (scores, ids) tensors to write into."""
+    dev = _lex_csr(row_ptr, terms, n, tf, doc_len)
+    _req(1 <= k <= 64, "1 <= k <= 64")
+    _req(0 <= nq <= LEX_MAX_QUERIES, "at most %d queries per launch" % LEX_MAX_QUERIES)
+    qt = _lex_table(qterms, dev)
+    T = qt.numel()
+    _req(idf.dtype == torch.float32 and idf.dim() == 1 and idf.numel() == T and idf.is_contiguous(), "idf fp32 [T]")
+    _req(member.dtype == torch.int64 and member.dim() == 1 and member.numel() == T and member.is_contiguous(),
+         "member int64 [T]")
+    idf, member = idf.to(dev), member.to(dev)
+    words = bits = 0
+    if masks is not None or qmask is not None:
+        masks, words, bits, qmask = _mask_args(masks, qmask, nq, mask_bits, dev)
+    od, oi = _search_out(nq, k, dev) if out is None else out
+    _req(od.dtype == torch.float32 and oi.dtype == torch.int64 and od.device == dev and oi.device == dev
+         and od.is_contiguous() and oi.is_contiguous() and tuple(od.shape) == (nq, k) and tuple(oi.shape) == (nq, k),
+         "out = (scores fp32 [nq, k], ids int64 [nq, k])")
+    if nq == 0:
+        return od, oi
+    L = _lib.lib()
+    G = L.ragk_lex_search_groups(n)
+    with _search_lock:
+        pv, pi = _search_partials(nq * G * k, dev)
+        check(L.ragk_lex_search(row_ptr.data_ptr(), terms.data_ptr(), tf.data_ptr(), doc_len.data_ptr(), n,
+                                qt.data_ptr(), idf.data_ptr(), member.data_ptr(), T, nq, float(k1), float(k1p1),
+                                float(b), float(avgdl), k, ptr(masks), words, bits, ptr(qmask), pv.data_ptr(),
+                                pi.data_ptr(), od.data_ptr(), oi.data_ptr(), stream_ptr()), "ragk_lex_search")
+    return od, oi

@@ -491,3 +491,106 @@ def l2_knn(xb, q, k):
     D[:, :kk] = dv[:, :kk]
     I[:, :kk] = di[:, :kk]
     return D, I
+
+
+# ----------------------------------------------------------------------------- BM25 lexical search
+# fp32 replicas of csrc/kernels/lexical.hip. Layout (index/lexical.py): a doc-major CSR -- row_ptr int64 [n + 1],
+# terms int32 (the uint32 term ids' bit patterns, ascending within a document), tf int16 (uint16 bit patterns),
+# doc_len int32 [n]. A launch's term table: qterms int32 [T] (uint32 bit patterns, ascending as unsigned,
+# distinct), idf fp32 [T], member int64 [T] (bit q set: query q holds the term).
+LEX_MAX_TERMS = 4096
+LEX_MAX_QUERIES = 64
+
+
+def _lex_hits(row_ptr, terms, n, qterms):
+    """The CSR entries whose term is in the table, in entry order: (document [h], table position [h], entry
+    index [h])."""
+    rp = row_ptr[:n + 1].cpu().long()
+    nnz = int(rp[n]) if n else 0
+    t = terms[:nnz].cpu().long() & 0xFFFFFFFF
+    qt = qterms.cpu().long() & 0xFFFFFFFF
+    T = qt.numel()
+    if T == 0 or nnz == 0:
+        z = torch.zeros(0, dtype=torch.int64)
+        return z, z, z
+    pos = torch.searchsorted(qt, t).clamp_(max=T - 1)
+    hit = torch.nonzero(qt[pos] == t).reshape(-1)
+    doc_of = torch.repeat_interleave(torch.arange(n), rp[1:] - rp[:-1])
+    return doc_of[hit], pos[hit], hit
+
+
+def _lex_table_ok(qterms):
+    qt = qterms.cpu().long() & 0xFFFFFFFF
+    if qt.numel() > LEX_MAX_TERMS:
+        raise ValueError("lexical search: at most %d terms per launch" % LEX_MAX_TERMS)
+    if qt.numel() > 1 and not bool((qt[1:] > qt[:-1]).all()):
+        raise ValueError("lexical search: the term table must be strictly ascending (as unsigned ids)")
+
+
+def _lex_allowed(masks, qmask, n):
+    from ..index.flat import mask_allowed
+
+    return torch.from_numpy(mask_allowed(masks, qmask, torch.arange(n).numpy()))
+
+
+def lex_df(row_ptr, terms, n, qterms, live=None):
+    """int32 [T]: the documents among the first n -- those whose bit is set in the bitmap row `live` (uint32 /
+    int32 words), or all of them -- that hold each table term."""
+    _lex_table_ok(qterms)
+    T = qterms.numel()
+    hd, ht, _ = _lex_hits(row_ptr, terms, n, qterms)
+    if live is not None and hd.numel():
+        lv = live.cpu() if isinstance(live, torch.Tensor) else live
+        ok = _lex_allowed(lv.reshape(1, -1), torch.zeros(1, dtype=torch.int32), n)[0]
+        ht = ht[ok[hd]]
+    return torch.bincount(ht, minlength=T).to(torch.int32)
+
+
+def lex_search(row_ptr, terms, tf, doc_len, n, qterms, idf, member, nq, k1, k1p1, b, avgdl, k, masks=None,
+               qmask=None):
+    """Top k documents per query by BM25 -> (scores fp32 [nq, k] descending, ids int64 [nq, k], ties -> lower id,
+    padding (0, -1)). The kernel's arithmetic, every operation rounded to fp32 on its own:
+        norm = k1 * ((1 - b) + b * (float(dl) / avgdl));  c = idf * ((float(tf) * k1p1) / (float(tf) + norm))
+    and a document's score is the sum of its matching terms' c in ascending term-id (= entry) order. A document
+    with no matching term is no candidate. masks / qmask: per-query id bitmaps as in the L2 search."""
+    _lex_table_ok(qterms)
+    if not 1 <= k <= 64 or not 0 <= nq <= LEX_MAX_QUERIES:
+        raise ValueError("lexical search: 1 <= k <= 64 and at most %d queries per launch" % LEX_MAX_QUERIES)
+    f32 = torch.float32
+    S = torch.zeros((nq, k), dtype=f32)
+    I = torch.full((nq, k), -1, dtype=torch.int64)
+    hd, ht, he = _lex_hits(row_ptr, terms, n, qterms)
+    if nq == 0 or hd.numel() == 0:
+        return S, I
+    k1, k1p1, b, avgdl = (torch.tensor(float(v), dtype=f32) for v in (k1, k1p1, b, avgdl))
+    ftf = (tf.cpu().long()[he] & 0xFFFF).to(f32)
+    dl = doc_len[:n].cpu().to(f32)
+    norm = k1 * ((torch.tensor(1.0, dtype=f32) - b) + b * (dl / avgdl))
+    c = idf.cpu().to(f32)[ht] * ((ftf * k1p1) / (ftf + norm[hd]))
+    bits = ((member.cpu().long()[ht].unsqueeze(1) >> torch.arange(nq)) & 1).bool()  # [hits, nq]
+    cnt = torch.bincount(hd, minlength=n)
+    rank = torch.arange(hd.numel()) - (torch.cumsum(cnt, 0) - cnt)[hd]  # a hit's place among its document's hits
+    order = torch.argsort(rank, stable=True)
+    per_rank = torch.bincount(rank).tolist()
+    score = torch.zeros((n, nq), dtype=f32)
+    matched = torch.zeros((n, nq), dtype=torch.bool)
+    zero = torch.zeros((), dtype=f32)
+    o0 = 0
+    for m in per_rank:  # the r-th hit of every document at once: one document per row, so the adds stay ordered
+        sel = order[o0:o0 + m]
+        o0 += m
+        d = hd[sel]
+        score[d] = score[d] + torch.where(bits[sel], c[sel].unsqueeze(1), zero)  # x + 0 == x: non-members keep theirs
+        matched[d] |= bits[sel]
+    cand = matched.t()
+    if masks is not None or qmask is not None:
+        mk = masks.cpu() if isinstance(masks, torch.Tensor) else masks
+        qm = qmask.cpu() if isinstance(qmask, torch.Tensor) else qmask
+        cand = cand & _lex_allowed(mk, qm, n)
+    key = torch.where(cand, -score.t(), torch.full((), float("inf"), dtype=f32))
+    kv, ki = torch.sort(key, dim=1, stable=True)  # ascending -score; equal scores keep ascending ids
+    kk = min(k, n)
+    ok = kv[:, :kk] != float("inf")
+    S[:, :kk] = torch.where(ok, -kv[:, :kk], S[:, :kk])
+    I[:, :kk] = torch.where(ok, ki[:, :kk], I[:, :kk])
+    return S, I

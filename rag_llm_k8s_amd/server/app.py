@@ -27,6 +27,10 @@ New (documents can be listed, removed, replaced and filtered on; the reference c
                      fp32 logits after the logit processors, before temperature / top-k / top-p, with the N most
                      likely alternatives per position; a bool, float, negative or > 20 value -> 400 {"error"}.
                      Without the field (and without LOGPROBS) the response keys are unchanged
+  POST /generate     optional "hybrid": true | false -> fuse (or not) the BM25 lexical list with the dense one for this
+                     query (HYBRID_SEARCH=rrf sets the default); "hybrid": true on a server without a lexical index,
+                     or a value that is no boolean -> 400 {"error"}. With "debug" the response's "retrieved" rows
+                     gain "dense_rank", "lexical_rank" (1-based, null = not in that list) and "lexical_score"
   POST /upload_pdf?replace=1 (or form field replace=1) -> the document's old chunks are replaced
   GET  /documents    -> {"documents": [{"filename", "chunks"}]}
   DELETE /documents/<filename> -> 200 {"message", "chunks_removed"} | 404 {"error"}
@@ -55,6 +59,15 @@ def create_app(service) -> Flask:
             kw = {"filenames": filenames} if filenames else {}
             if data.get("rerank") is not None:  # per-request switch of the cross-encoder stage
                 kw["rerank"] = bool(data["rerank"])
+            if data.get("hybrid") is not None:  # per-request switch of the BM25 + dense fusion
+                if not isinstance(data["hybrid"], bool):
+                    metrics.inc("requests", route="generate", status="400")
+                    return jsonify({"error": '"hybrid" must be true or false (got %r)' % (data["hybrid"],)}), 400
+                try:
+                    kw["hybrid"] = service._hybrid_flag(data["hybrid"])
+                except ValueError as e:  # no lexical index on this server
+                    metrics.inc("requests", route="generate", status="400")
+                    return jsonify({"error": str(e)}), 400
             # per-request logit processors: the service's default SamplingParams with these fields replaced
             over = {k: data[k] for k in service.REQUEST_PARAM_FIELDS if data.get(k) is not None}
             if over:

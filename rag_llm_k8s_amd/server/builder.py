@@ -143,11 +143,13 @@ def build_service(cfg, start_threads=True, tp_rank=0, tp_size=1, comm=None, tp_g
     log.info("Model and tokenizer loaded successfully")
     embedder = build_embedder(cfg, device)
     shard = None
+    cfg.validate_hybrid()  # refuses HYBRID_SEARCH=rrf with INDEX_SHARDED before anything is loaded into the store
     if cfg.index_sharded and tp_size > 1:
         shard = (tp_group, tp_rank, tp_size)  # INDEX_SHARDED=1: row shard per TP rank (parallel/dp.py)
     store = DocumentStore(cfg.index_path, embedder.dim, device=device, index_type=cfg.index_type,
                           ivf_nlist=cfg.ivf_nlist, ivf_nprobe=cfg.ivf_nprobe, recovery=cfg.index_recovery,
-                          shard=shard)
+                          shard=shard, lexical=cfg.hybrid, hybrid_candidates=cfg.hybrid_candidates,
+                          bm25_k1=cfg.bm25_k1, bm25_b=cfg.bm25_b, rrf_k=cfg.rrf_k)
     reranker = build_reranker(cfg, device) if tp_rank == 0 else None  # like the query embedder: rank 0 retrieves
     svc = RagService(cfg, engine, tok, embedder, store, gen_config=gen, start_threads=start_threads, control=control,
                      tp_group=tp_group if tp_size > 1 else None, reranker=reranker)

@@ -355,12 +355,15 @@ class RagService:
         return out
 
     def _retrieve_batch(self, items):
-        """items: (prompt, filter[, rerank]) tuples -- filter None, or the filenames the context must come
-        from; rerank False skips the second stage for that query. The micro-batcher mixes requests, so one
-        search carries a filter per query (a masked search) and one batch may hold both kinds of query."""
+        """items: (prompt, filter[, rerank[, hybrid]]) tuples -- filter None, or the filenames the context must
+        come from; rerank False skips the second stage for that query; hybrid True / False switches the BM25 +
+        dense fusion for that query (None = the configured default). The micro-batcher mixes requests, so one
+        search carries a filter per query (a masked search) and one batch may hold every kind of query: the
+        queries that do not want hybrid get exactly the dense result."""
         prompts = [it[0] for it in items]
         filters = [it[1] for it in items]
         want = [self.reranker is not None and (len(it) < 3 or it[2] is not False) for it in items]
+        hyb = [self._hybrid_on(it[3] if len(it) > 3 else None) for it in items]
         k_search = self._search_k(want)
         tr = Trace("retrieve")
         with tr.span("embed"):
@@ -370,6 +373,9 @@ class RagService:
             self.store.maybe_reload()
             if self.collective and getattr(self.store, "sharded", False):
                 res = self.loop.run_job("search", (q.cpu(), k_search), timeout=self.cfg.request_timeout_s)
+            elif any(hyb):  # the spans "lexical" and "fuse" are recorded inside
+                res = self.store.search(q, k_search, filters=filters if any(f is not None for f in filters) else None,
+                                        texts=[p if h else None for p, h in zip(prompts, hyb)], trace=tr)
             elif any(f is not None for f in filters):
                 res = self.store.search(q, k_search, filters=filters)
             else:
@@ -396,11 +402,25 @@ class RagService:
             raise ValueError('"rerank": true needs a reranker: set RERANK_MODEL to a cross-encoder directory')
         return bool(rerank)
 
-    def retrieve(self, prompt, filenames=None, rerank=None):
+    def _hybrid_flag(self, hybrid):
+        """Request "hybrid": absent = the configured default; true needs a store with a lexical index."""
+        if hybrid is None:
+            return None
+        if hybrid and getattr(self.store, "lexical", None) is None:
+            raise ValueError('"hybrid": true needs a lexical index: set HYBRID_SEARCH=rrf')
+        return bool(hybrid)
+
+    def _hybrid_on(self, flag):
+        """Does a query with this (checked) flag run hybrid? None = HYBRID_SEARCH's default."""
+        if getattr(self.store, "lexical", None) is None:
+            return False
+        return bool(getattr(self.cfg, "hybrid", False)) if flag is None else bool(flag)
+
+    def retrieve(self, prompt, filenames=None, rerank=None, hybrid=None):
         flt = self._filter(filenames)
         if flt is not None and getattr(self.store, "sharded", False):  # refused before it joins a batch
             raise ValueError(self.store.SHARDED_REFUSAL % "filtering")
-        return self.batcher.submit((prompt, flt, self._rerank_flag(rerank)))
+        return self.batcher.submit((prompt, flt, self._rerank_flag(rerank), self._hybrid_flag(hybrid)))
 
     # ------------------------------------------------------------------ generation
     def _next_seed(self):
@@ -495,11 +515,12 @@ class RagService:
         self.engine.check_params(p)
         return p
 
-    def generate(self, user_prompt, params=None, debug=False, filenames=None, rerank=None):
+    def generate(self, user_prompt, params=None, debug=False, filenames=None, rerank=None, hybrid=None):
         """Synchronous /generate (thread-safe). filenames: only these documents supply the context.
-        rerank: False skips the cross-encoder stage for this request (None = on when one is configured)."""
+        rerank: False skips the cross-encoder stage for this request (None = on when one is configured).
+        hybrid: True / False switches BM25 + dense fusion for this request (None = HYBRID_SEARCH's default)."""
         tr = Trace("generate")
-        results, rspans = self.retrieve(user_prompt, filenames, rerank)
+        results, rspans = self.retrieve(user_prompt, filenames, rerank, hybrid)
         for k, v in rspans.items():
             tr.spans[k] = v
         log.debug("User query: %s", user_prompt)
@@ -541,13 +562,21 @@ class RagService:
                 out["retrieved"] = [{"filename": m.get("filename"), "chunk_id": m.get("chunk_id"),
                                      "distance": float(d), "rerank_score": m.get("rerank_score")}
                                     for m, d in results]
+            if self._hybrid_on(self._hybrid_flag(hybrid)):  # the fused lists: where each chunk came from
+                rows = out.setdefault("retrieved", [{"filename": m.get("filename"), "chunk_id": m.get("chunk_id"),
+                                                     "distance": float(d)} for m, d in results])
+                for row, (m, _) in zip(rows, results):
+                    row.update(dense_rank=m.get("dense_rank"), lexical_rank=m.get("lexical_rank"),
+                               lexical_score=m.get("lexical_score"))
         return out
 
-    def generate_batch(self, prompts, params=None, seeds=None, filters=None, rerank=None):
+    def generate_batch(self, prompts, params=None, seeds=None, filters=None, rerank=None, hybrid=None):
         """Many queries at once (benchmark / offline): one embed + one search + one engine run.
         filters: per prompt None or the filenames its context must come from.
         rerank: per prompt (or one value for all) False to skip the cross-encoder stage; None = on when a
         reranker is configured. With a reranker the outputs also carry "_retrieved": [(filename, chunk_id)].
+        hybrid: per prompt (or one value for all) True / False for BM25 + dense fusion; None = HYBRID_SEARCH's
+        default. A prompt that does not run hybrid gets exactly the dense result.
         Must not be mixed with the background loop (call with start_threads=False).
 
         Tensor parallel (every TP rank calls this with the same arguments): the TP leader embeds,
@@ -570,7 +599,13 @@ class RagService:
             want = [self.reranker is not None and self._rerank_flag(f) is not False for f in flags]
             k_search = self._search_k(want)
             q = self.embedder.embed(list(prompts))
-            if filters is not None and any(f for f in filters):
+            hflags = list(hybrid) if isinstance(hybrid, (list, tuple)) else [hybrid] * n
+            hyb = [self._hybrid_on(self._hybrid_flag(f)) for f in hflags]
+            if any(hyb):
+                fl = [self._filter(f) for f in filters] if filters is not None and any(f for f in filters) else None
+                res = self.store.search(q, k_search, filters=fl,
+                                        texts=[p if h else None for p, h in zip(prompts, hyb)])
+            elif filters is not None and any(f for f in filters):
                 res = self.store.search(q, k_search, filters=[self._filter(f) for f in filters])
             else:
                 res = self.store.search(q, k_search)

@@ -144,13 +144,15 @@ def build_workload(model="8b", embedder="minilm", n_chunks=10000, chunk_words=10
                    ctx=None, tp_comm=None, seed=0, use_graphs=True, index_type="flat", kv_blocks=None,
                    word_vocab=400000, dtype="bf16", index_vectors=0, start_threads=False, ignore_eos=False,
                    mixed_prefill_tokens=0, progress=None, kv_dtype=None, reranker=None, rerank_candidates=32,
-                   rerank_max_len=512):
+                   rerank_max_len=512, hybrid=None, hybrid_candidates=32):
     """`reranker`: None (off) or an encoder shape name ("tiny", "minilm", "bge-large"): a random-init
     cross-encoder of that shape is attached as the second retrieval stage (BERT shapes: it shares the
     embedder's WordPiece tokenizer), searching `rerank_candidates` chunks per query.
     `progress(msg)`: called after each setup stage (bench.py prints it: a 70B / 1M-vector setup runs
     for minutes). `kv_dtype`: "bf16" | "fp8" KV cache; None takes the KV_CACHE_DTYPE environment variable
-    (default bf16), so bench.py and tools/bench_serve.py can be A/B-run unmodified."""
+    (default bf16), so bench.py and tools/bench_serve.py can be A/B-run unmodified.
+    `hybrid`: "off" | "rrf" (a BM25 index over the chunk texts, fused with the dense list by reciprocal rank,
+    both `hybrid_candidates` deep); None takes the HYBRID_SEARCH environment variable (default off)."""
     import os
 
     from ..ops.fp8 import kv_cache_dtype_name
@@ -223,10 +225,15 @@ def build_workload(model="8b", embedder="minilm", n_chunks=10000, chunk_words=10
                     max_batch=max_batch, max_model_len=max_model_len, index_path="/tmp/ragk_bench_index",
                     index_type=index_type, seed=seed, max_prefill_tokens=max_prefill_tokens, ignore_eos=ignore_eos,
                     mixed_prefill_tokens=mixed_prefill_tokens, kv_cache_dtype=kv_dtype,
-                    rerank_candidates=max(retrieve_k, rerank_candidates), rerank_max_len=rerank_max_len)
+                    rerank_candidates=max(retrieve_k, rerank_candidates), rerank_max_len=rerank_max_len,
+                    hybrid_search=(os.environ.get("HYBRID_SEARCH") or "off") if hybrid is None else hybrid,
+                    hybrid_candidates=hybrid_candidates)
+    cfg.validate_hybrid()
     n_index = max(n_chunks, index_vectors)
     store = DocumentStore(cfg.index_path, emb.dim, device=device, index_type=index_type,
-                          ivf_nlist=4096 if n_index >= 500_000 else 1024)
+                          ivf_nlist=4096 if n_index >= 500_000 else 1024, lexical=cfg.hybrid,
+                          hybrid_candidates=cfg.hybrid_candidates, bm25_k1=cfg.bm25_k1, bm25_b=cfg.bm25_b,
+                          rrf_k=cfg.rrf_k)
     vecs = emb.embed(chunks)
     if device.startswith("cuda"):
         torch.cuda.synchronize()
