@@ -8,10 +8,12 @@
 // Nothing accumulates (no counts, no bitmaps) in global memory: the counts of the frequency / presence penalties
 // live in LDS for the length of one launch.
 //
-// logits_process_pen_kernel is the same chain with the OpenAI-style controls around it: logit_bias first, then
-// the repetition penalty, then frequency / presence over the GENERATED tokens, then the -inf writes. It is a
-// kernel of its own that repeats the shared phases: logits_process_kernel and ragk_logits_process are unchanged,
-// instruction for instruction.
+// One chain, two entry points. Per logits row: history store, [logit_bias], repetition penalty, [frequency /
+// presence over the GENERATED tokens], then the -inf writes of the n-gram ban and the ban list. The bracketed
+// phases are the OpenAI-style controls; only logits_process_pen_kernel has them, so a step without such a row
+// launches logits_process_kernel and pays nothing for them. The phases both kernels run are the lp_* device
+// functions below, which take plain values and pointers (each kernel keeps its own early exit and history
+// store: the kernarg loads then stay where they are needed).
 #include "common.h"
 #include <math.h>
 using namespace ragk;
@@ -40,14 +42,60 @@ __global__ __launch_bounds__(LP_THREADS) void hist_write_kernel(const int* __res
   hist[(size_t)r * ld + p] = ids[i];
 }
 
+// Repetition penalty of one row (history h[0 .. L), logits lrow): every history entry's ORIGINAL logit is staged
+// in LDS before any thread of the row writes one; then every entry writes f(original). Duplicate ids write the
+// same value, so the penalty applies once per distinct id without atomics or a dedupe pass. Ends in a barrier:
+// later writes win over the penalty, and the stage is free.
+__device__ __forceinline__ void lp_repetition(float* lrow, int V, int vocab_offset, const int* h, int L, float pen,
+                                              float* stage, int tid) {
+  if (pen == 1.0f) return;  // block-uniform; x * 1 and x / 1 are x, so skipping is exact
+#pragma unroll 4
+  for (int i = tid; i < L; i += LP_THREADS) {
+    const int t = h[i] - vocab_offset;
+    stage[i] = (t >= 0 && t < V) ? lrow[t] : 0.f;
+  }
+  __syncthreads();  // every original logit is read before any is written
+#pragma unroll 4
+  for (int i = tid; i < L; i += LP_THREADS) {
+    const int t = h[i] - vocab_offset;
+    if (t >= 0 && t < V) {
+      const float x = stage[i];
+      lrow[t] = x < 0.f ? x * pen : x / pen;
+    }
+  }
+  __syncthreads();
+}
+
+// The -inf writes of one row: the n-gram ban (size n) over its history, then the first min(*ban_count, ban_ld) ids
+// of its ban list (min_new_tokens). The count is read here, after the n-gram pass, where the kernels always read it.
+__device__ __forceinline__ void lp_bans(float* lrow, int V, int vocab_offset, const int* h, int L, int n,
+                                        const int* __restrict__ ban, int ban_ld, const int* __restrict__ ban_count,
+                                        int tid) {
+  if (n >= 1 && n <= LP_MAX_NGRAM && L >= n) {
+    // the last n-1 tokens; every earlier occurrence of them bans the token that followed it
+    const int* suf = h + (L - n + 1);
+    for (int j = tid; j <= L - n; j += LP_THREADS) {
+      bool match = true;
+      for (int k = 0; k < n - 1; ++k) match &= h[j + k] == suf[k];
+      if (match) {
+        const int t = h[j + n - 1] - vocab_offset;
+        if (t >= 0 && t < V) lrow[t] = -INFINITY;
+      }
+    }
+  }
+  const int nb = min(*ban_count, ban_ld);
+  for (int i = tid; i < nb; i += LP_THREADS) {
+    const int t = ban[i] - vocab_offset;
+    if (t >= 0 && t < V) lrow[t] = -INFINITY;
+  }
+}
+
 // One workgroup (LP_THREADS threads) per logits row b (history row rows[b], length pos[b] + 1).
 //   1. rows[b] < 0: nothing is touched (padded graph rows, rows of requests without processors).
 //   2. ids given (decode): hist[row][pos[b]] = ids[b] first -- ids[b] is the id the embedding kernel
 //      resolved (carried rows included), so this launch comes after the embedding.
-//   3. repetition penalty: every history entry's ORIGINAL logit is staged in LDS before any thread of the row
-//      writes one; then every entry writes f(original). Duplicate ids write the same value, so the
-//      penalty applies once per distinct id without atomics or a dedupe pass.
-//   4. after a barrier: the -inf writes of the n-gram ban and of the min_new_tokens ban list.
+//   3. repetition penalty (lp_repetition).
+//   4. the -inf writes of the n-gram ban and of the min_new_tokens ban list (lp_bans).
 // Ids outside [vocab_offset, vocab_offset + V) belong to another tensor-parallel vocab shard and are skipped.
 __global__ __launch_bounds__(LP_THREADS) void logits_process_kernel(
     float* logits, int ld, int V, int vocab_offset, const int* __restrict__ ids,
@@ -67,43 +115,8 @@ __global__ __launch_bounds__(LP_THREADS) void logits_process_kernel(
   const int L = min(max(p + 1, 0), hist_ld);
   float* lrow = logits + (size_t)b * ld;
 
-  const float pen = penalty[b];
-  if (pen != 1.0f) {  // block-uniform; x * 1 and x / 1 are x, so skipping is exact
-#pragma unroll 4
-    for (int i = tid; i < L; i += LP_THREADS) {
-      const int t = h[i] - vocab_offset;
-      stage[i] = (t >= 0 && t < V) ? lrow[t] : 0.f;
-    }
-    __syncthreads();  // every original logit is read before any is written
-#pragma unroll 4
-    for (int i = tid; i < L; i += LP_THREADS) {
-      const int t = h[i] - vocab_offset;
-      if (t >= 0 && t < V) {
-        const float x = stage[i];
-        lrow[t] = x < 0.f ? x * pen : x / pen;
-      }
-    }
-    __syncthreads();  // the -inf writes below win over the penalty
-  }
-
-  const int n = ngram[b];
-  if (n >= 1 && n <= LP_MAX_NGRAM && L >= n) {
-    // the last n-1 tokens; every earlier occurrence of them bans the token that followed it
-    const int* suf = h + (L - n + 1);
-    for (int j = tid; j <= L - n; j += LP_THREADS) {
-      bool match = true;
-      for (int k = 0; k < n - 1; ++k) match &= h[j + k] == suf[k];
-      if (match) {
-        const int t = h[j + n - 1] - vocab_offset;
-        if (t >= 0 && t < V) lrow[t] = -INFINITY;
-      }
-    }
-  }
-  const int nb = min(ban_count[b], ban_ld);
-  for (int i = tid; i < nb; i += LP_THREADS) {
-    const int t = ban_ids[(size_t)b * ban_ld + i] - vocab_offset;
-    if (t >= 0 && t < V) lrow[t] = -INFINITY;
-  }
+  lp_repetition(lrow, V, vocab_offset, h, L, penalty[b], stage, tid);
+  lp_bans(lrow, V, vocab_offset, h, L, ngram[b], ban_ids + (size_t)b * ban_ld, ban_ld, ban_count + b, tid);
 }
 
 // Counting table of the frequency / presence penalties: open addressing with linear probing over `slots` (a power
@@ -123,16 +136,16 @@ __device__ __forceinline__ float lp_freq_pres(float x, float freq, float c, floa
   return y - pres;
 }
 
-// The chain of logits_process_kernel with logit_bias, frequency and presence penalties:
-//   1. history store (decode), as above.
+// The chain with its optional phases, logit_bias and the frequency / presence penalties:
+//   1. early exit and history store (decode), as above.
 //   2. bias: thread i < bias_count[b] adds bias_vals[row][i] to the logit of bias_ids[row][i]. The ids of a table
 //      row are distinct (admission), so one read-add-write per thread needs no atomics. The tables are indexed
 //      by the HISTORY row: they are written once per sequence, not per step.
-//   3. repetition penalty, on the biased values.
+//   3. repetition penalty (lp_repetition), on the biased values.
 //   4. frequency, then presence, over the generated tokens h[gen_start .. L): every distinct id t with count c
 //      gets (x - frequency * float(c)) - presence, three separately rounded fp32 operations (what torch's
 //      x -= f * c; x -= p computes; no FMA contraction). Skipped block-uniformly when both are 0.
-//   5. the -inf writes, which win.
+//   5. the -inf writes (lp_bans), which win.
 // The table takes min(tslots, the power of two >= 2 * generated) slots; the launcher sizes tslots for the host's
 // bound on the generated span. A row whose span exceeds its table (the host's bound was wrong) loses counts, it
 // never loops: every probe run is bounded by the slot count.
@@ -165,24 +178,7 @@ __global__ __launch_bounds__(LP_THREADS) void logits_process_pen_kernel(
     __syncthreads();  // the phases below read the biased values
   }
 
-  const float pen = penalty[b];
-  if (pen != 1.0f) {  // block-uniform; the phase of logits_process_kernel, verbatim
-#pragma unroll 4
-    for (int i = tid; i < L; i += LP_THREADS) {
-      const int t = h[i] - vocab_offset;
-      stage[i] = (t >= 0 && t < V) ? lrow[t] : 0.f;
-    }
-    __syncthreads();  // every original logit is read before any is written
-#pragma unroll 4
-    for (int i = tid; i < L; i += LP_THREADS) {
-      const int t = h[i] - vocab_offset;
-      if (t >= 0 && t < V) {
-        const float x = stage[i];
-        lrow[t] = x < 0.f ? x * pen : x / pen;
-      }
-    }
-    __syncthreads();  // the stage is free from here on
-  }
+  lp_repetition(lrow, V, vocab_offset, h, L, penalty[b], stage, tid);  // the stage is free from here on
 
   const float pres = presence[b], freq = frequency[b];
   const int g0 = min(max(gen_start[b], 0), L);
@@ -218,23 +214,20 @@ __global__ __launch_bounds__(LP_THREADS) void logits_process_pen_kernel(
     __syncthreads();  // the -inf writes below win over the penalties
   }
 
-  const int n = ngram[b];
-  if (n >= 1 && n <= LP_MAX_NGRAM && L >= n) {
-    const int* suf = h + (L - n + 1);
-    for (int j = tid; j <= L - n; j += LP_THREADS) {
-      bool match = true;
-      for (int k = 0; k < n - 1; ++k) match &= h[j + k] == suf[k];
-      if (match) {
-        const int t = h[j + n - 1] - vocab_offset;
-        if (t >= 0 && t < V) lrow[t] = -INFINITY;
-      }
-    }
+  lp_bans(lrow, V, vocab_offset, h, L, ngram[b], ban_ids + (size_t)b * ban_ld, ban_ld, ban_count + b, tid);
+}
+
+// What both launchers check of their arguments, and the opt-in to more than 64 KiB of dynamic LDS, taken once
+// per kernel (*opted). 0, or the hipError_t to return.
+int lp_prepare(const void* kernel, bool* opted, int ld, int V, int hist_rows, int hist_ld, int ban_ld) {
+  if (V < 1 || ld < V || hist_rows < 1 || hist_ld < 1 || hist_ld > LP_MAX_HIST || ban_ld < 1)
+    return (int)hipErrorInvalidValue;
+  if (!*opted) {
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LP_MAX_HIST * 4);
+    if (e != hipSuccess) return (int)e;
+    *opted = true;
   }
-  const int nb = min(ban_count[b], ban_ld);
-  for (int i = tid; i < nb; i += LP_THREADS) {
-    const int t = ban_ids[(size_t)b * ban_ld + i] - vocab_offset;
-    if (t >= 0 && t < V) lrow[t] = -INFINITY;
-  }
+  return 0;
 }
 
 }  // namespace
@@ -257,15 +250,8 @@ RAGK_API int ragk_logits_process(float* logits, int ld, int B, int V, int vocab_
                                  const float* penalty, const int* ngram, const int* ban_ids, int ban_ld,
                                  const int* ban_count, hipStream_t st) {
   if (B <= 0) return 0;
-  if (V < 1 || ld < V || hist_rows < 1 || hist_ld < 1 || hist_ld > LP_MAX_HIST || ban_ld < 1)
-    return (int)hipErrorInvalidValue;
-  static bool attr = false;  // > 64 KiB of dynamic LDS needs the opt-in
-  if (!attr) {
-    const hipError_t e = hipFuncSetAttribute((const void*)logits_process_kernel,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, LP_MAX_HIST * 4);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
+  static bool attr = false;
+  if (const int e = lp_prepare((const void*)logits_process_kernel, &attr, ld, V, hist_rows, hist_ld, ban_ld)) return e;
   hipLaunchKernelGGL(logits_process_kernel, dim3(B), dim3(LP_THREADS), (size_t)hist_ld * 4, st, logits, ld, V,
                      vocab_offset, ids, rows, pos, hist, hist_rows, hist_ld, penalty, ngram, ban_ids, ban_ld,
                      ban_count);
@@ -275,7 +261,7 @@ RAGK_API int ragk_logits_process(float* logits, int ld, int B, int V, int vocab_
 RAGK_API int ragk_logits_proc_pen_gen_max() { return LP_PEN_GEN_MAX; }
 RAGK_API int ragk_logits_proc_bias_max() { return LP_BIAS_MAX; }
 
-// ragk_logits_process with logit_bias and frequency / presence penalties (logits_process_pen_kernel). The new
+// ragk_logits_process with logit_bias and frequency / presence penalties (logits_process_pen_kernel). Its further
 // per-row arguments: gen_start (prompt length), presence, frequency, bias_count [B]; bias_ids / bias_vals
 // [hist_rows][bias_ld], indexed by history row. gen_bound: the host's bound on pos[b] - gen_start[b] + 1 over
 // the rows with a penalty; it sizes the counting table and is refused above LP_PEN_GEN_MAX.
@@ -286,18 +272,12 @@ RAGK_API int ragk_logits_process_pen(float* logits, int ld, int B, int V, int vo
                                      const float* frequency, const int* bias_count, const int* bias_ids,
                                      const float* bias_vals, int bias_ld, int gen_bound, hipStream_t st) {
   if (B <= 0) return 0;
-  if (V < 1 || ld < V || hist_rows < 1 || hist_ld < 1 || hist_ld > LP_MAX_HIST || ban_ld < 1 || bias_ld < 1 ||
-      gen_bound < 0 || gen_bound > LP_PEN_GEN_MAX)
-    return (int)hipErrorInvalidValue;
+  if (bias_ld < 1 || gen_bound < 0 || gen_bound > LP_PEN_GEN_MAX) return (int)hipErrorInvalidValue;
+  static bool attr = false;
+  if (const int e = lp_prepare((const void*)logits_process_pen_kernel, &attr, ld, V, hist_rows, hist_ld, ban_ld))
+    return e;
   int tslots = LP_PEN_MIN_SLOTS;
   while (tslots < 2 * gen_bound) tslots <<= 1;  // <= LP_PEN_MAX_SLOTS
-  static bool attr = false;  // > 64 KiB of dynamic LDS needs the opt-in
-  if (!attr) {
-    const hipError_t e = hipFuncSetAttribute((const void*)logits_process_pen_kernel,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, LP_MAX_HIST * 4);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
   const size_t lds = max((size_t)hist_ld * 4, (size_t)tslots * 8);
   hipLaunchKernelGGL(logits_process_pen_kernel, dim3(B), dim3(LP_THREADS), lds, st, logits, ld, V, vocab_offset, ids,
                      rows, pos, hist, hist_rows, hist_ld, penalty, ngram, ban_ids, ban_ld, ban_count, gen_start,

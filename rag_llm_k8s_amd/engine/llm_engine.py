@@ -19,6 +19,7 @@ Here:
 """
 from __future__ import annotations
 
+import gc
 import itertools
 import logging
 import math
@@ -42,6 +43,7 @@ from ..ops.reference import LOGPROBS_MAX, lse_chunks
 from ..ops.reference import LOGIT_BIAS_MAX, PENALTY_GEN_MAX
 from ..utils import faults
 from .kv_manager import BLOCK, make_block_manager
+from .step_layout import BAN_IDS_MAX, StepLayout, graph_key
 
 # decode batches up to this size split each row's top-k over ~31 chunks of ~4k logits (topk_wave_kernel,
 # threshold-filtered lane networks, merged by the sampler's lane network); larger batches use 7
@@ -50,10 +52,8 @@ from .kv_manager import BLOCK, make_block_manager
 SMALL_BATCH_TOPK_MAX_B = 64
 SMALL_BATCH_TOPK_CHUNK = 4096
 
-# history-dependent logit processors (csrc/kernels/logits_proc.hip): widest n-gram ban, and the width of the
-# per-row ban id table (the ids a request stops on, banned while it has fewer than min_new_tokens tokens)
+# history-dependent logit processors (csrc/kernels/logits_proc.hip): widest n-gram ban
 NGRAM_MAX = 8
-BAN_IDS_MAX = 16
 
 log = logging.getLogger(__name__)
 
@@ -353,75 +353,29 @@ class LLMEngine:
             self._hist_free.extend(self._hist_after)
             self._hist_after = []
 
-    PEN_WORDS = 4  # per-row words of the penalty form: gen_start | presence (f32) | frequency (f32) | bias count
+    def _step_key(self, seqs, full_vocab=False):
+        """The graph variant (and the sections of the step block) a sampling step over `seqs` needs, counted in
+        the stats. A full-vocabulary step computes its logprobs on the host: it counts as a logprob step and
+        needs no logprob section."""
+        proc = any(s.hist_row >= 0 for s in seqs)
+        pen = any(s.hist_row >= 0 and s.params.uses_penalties() for s in seqs)
+        lp = any(s.logprobs is not None for s in seqs)
+        self.stats["logit_proc_steps"] += int(proc)
+        self.stats["penalty_steps"] += int(pen)
+        self.stats["logprob_steps"] += int(lp)
+        return graph_key(self._bucket(len(seqs)), proc, lp and not full_vocab, pen)
 
-    @staticmethod
-    def _uses_penalties(seqs):
-        """True if a row of the step needs the penalty form of the processor launch."""
-        return any(s.hist_row >= 0 and s.params.uses_penalties() for s in seqs)
+    def _pack(self, layout, seqs, carried=None):
+        return layout.pack(seqs, carried, top_k_cap=self.K, stop_ids=self._stop_ids, bt_row=self._bt_row)
 
-    def _proc_host(self, seqs, gen, pad_to=None, penalties=False):
-        """int32 [(4 + BAN_IDS_MAX) n] = history rows | penalty (f32) | n-gram size | ban count | ban ids [n, W].
-        gen[i]: tokens sequence i has generated before the one being sampled. Plain and padded rows: row -1.
-        penalties: PEN_WORDS * n more words, gen_start (the prompt length) | presence | frequency | bias count."""
-        n = pad_to or len(seqs)
-        rows = np.full(n, -1, dtype=np.int32)
-        pen = np.ones(n, dtype=np.float32)
-        ng = np.zeros(n, dtype=np.int32)
-        cnt = np.zeros(n, dtype=np.int32)
-        ban = np.zeros((n, BAN_IDS_MAX), dtype=np.int32)
-        for i, s in enumerate(seqs):
-            if s.hist_row < 0:
-                continue
-            p = s.params
-            rows[i], pen[i], ng[i] = s.hist_row, p.repetition_penalty, p.no_repeat_ngram_size
-            if not p.ignore_eos and gen[i] < p.min_new_tokens:
-                stop = self._stop_ids(p)
-                cnt[i] = len(stop)
-                ban[i, :len(stop)] = stop
-        parts = [rows, pen.view(np.int32), ng, cnt, ban.reshape(-1)]
-        if penalties:
-            g0 = np.zeros(n, dtype=np.int32)
-            pres = np.zeros(n, dtype=np.float32)
-            freq = np.zeros(n, dtype=np.float32)
-            nbias = np.zeros(n, dtype=np.int32)
-            for i, s in enumerate(seqs):
-                if s.hist_row < 0:
-                    continue
-                p = s.params
-                g0[i], pres[i], freq[i], nbias[i] = len(s.prompt), p.presence_penalty, p.frequency_penalty, \
-                    len(p.logit_bias)
-            parts += [g0, pres.view(np.int32), freq.view(np.int32), nbias]
-        return np.concatenate(parts)
-
-    @staticmethod
-    def _proc_views(buf, n, penalties=False):
-        v = dict(rows=buf[0:n], penalty=buf[n:2 * n].view(torch.float32), ngram=buf[2 * n:3 * n],
-                 ban_count=buf[3 * n:4 * n], ban_ids=buf[4 * n:(4 + BAN_IDS_MAX) * n].view(n, BAN_IDS_MAX))
-        if penalties:
-            o = (4 + BAN_IDS_MAX) * n
-            v.update(gen_start=buf[o:o + n], presence=buf[o + n:o + 2 * n].view(torch.float32),
-                     frequency=buf[o + 2 * n:o + 3 * n].view(torch.float32), bias_count=buf[o + 3 * n:o + 4 * n])
-        return v
-
-    def _proc_tensors(self, seqs, pos, gen, ids=None):
-        """Processor argument block of an eager sampling call (None if no row of it has a history row).
-        pos[i]: position of sequence i's last token (history length - 1); ids: decode input ids, stored into
-        the history by the kernel, or None when the history is already complete (prefill's sampled rows). A
-        call with a row that uses the penalty fields carries their words too (the penalty form of the launch)."""
-        if not any(s.hist_row >= 0 for s in seqs):
-            return None
-        n = len(seqs)
-        pen = self._uses_penalties(seqs)
-        buf = self._h2d_i32(np.concatenate([self._proc_host(seqs, gen, penalties=pen),
-                                            np.asarray(pos, dtype=np.int32)]))
-        proc = self._proc_views(buf, n, penalties=pen)
-        o = (4 + BAN_IDS_MAX + (self.PEN_WORDS if pen else 0)) * n
-        proc["pos"] = buf[o:o + n]
-        proc["ids"] = ids
-        return proc
+    def _eager_block(self, seqs, key, max_blocks=0):
+        """Views of the step block of an eager sampling call over exactly `seqs`, on the device (one H2D copy)."""
+        layout = StepLayout(len(seqs), max_blocks, key.processors, key.penalties, key.logprobs)
+        return layout.views(self._h2d_i32(self._pack(layout, seqs)))
 
     def _apply_processors(self, lg, proc):
+        """proc: the views of a step block with the processor section. proc["ids"]: the step's input ids, stored
+        into the history by the kernel, or None when the history is already complete (prefill's sampled rows)."""
         be = self.model.be
         if "gen_start" not in proc:
             be.logits_process(lg, self.model.w.vocab_offset, proc["ids"], proc["rows"], proc["pos"], self._hist,
@@ -438,14 +392,6 @@ class LLMEngine:
     # ------------------------------------------------------------------ per-token log-probabilities
     LP_WORDS = 2 + 2 * LOGPROBS_MAX  # output words per row: lse | token logprob | top logprobs | top ids
 
-    def _lp_host(self, seqs, pad_to=None):
-        """int32 [n]: alternatives per row, -1 for plain and padded rows."""
-        nlp = np.full(pad_to or len(seqs), -1, dtype=np.int32)
-        for i, s in enumerate(seqs):
-            if s.logprobs is not None:
-                nlp[i] = s.params.logprobs
-        return nlp
-
     @staticmethod
     def _lp_views(buf, n):
         """(lse [n], token logprob [n], top logprobs [n, LOGPROBS_MAX], top ids [n, LOGPROBS_MAX]) views of an
@@ -454,15 +400,12 @@ class LLMEngine:
         return (buf[0:n].view(torch.float32), buf[n:2 * n].view(torch.float32),
                 buf[2 * n:(2 + L) * n].view(torch.float32).view(n, L), buf[(2 + L) * n:(2 + 2 * L) * n].view(n, L))
 
-    def _lp_block(self, seqs):
-        """Logprob argument block of an eager sampling call (None if no row asks): nlp on the device and a
-        fresh output buffer."""
-        if not any(s.logprobs is not None for s in seqs):
+    def _lp_block(self, v, n):
+        """Logprob argument block of a sampling call over the n rows of the step block views v (None without a
+        logprob section): the rows' alternative counts and a fresh output buffer."""
+        if "nlp" not in v:
             return None
-        self.stats["logprob_steps"] += 1
-        n = len(seqs)
-        return dict(nlp=self._h2d_i32(self._lp_host(seqs)), n=n,
-                    buf=torch.zeros(self.LP_WORDS * n, dtype=torch.int32, device=self.device))
+        return dict(nlp=v["nlp"], n=n, buf=torch.zeros(self.LP_WORDS * n, dtype=torch.int32, device=self.device))
 
     def _lp_values(self, host, n, seqs):
         """Per sequence None or (token logprob, [(id, logprob)] of its N alternatives) from a host copy of an
@@ -671,34 +614,6 @@ class LLMEngine:
             return "length"
         return None
 
-    def _sampling_host(self, seqs, pad_to=None):
-        """int32 [6n] = seeds (int64, n) | temps (f32) | top_p (f32) | top_k | steps -- one H2D copy."""
-        n = pad_to or len(seqs)
-        seeds = np.zeros(n, dtype=np.int64)
-        temps = np.zeros(n, dtype=np.float32)
-        ps = np.ones(n, dtype=np.float32)
-        ks = np.ones(n, dtype=np.int32)
-        steps = np.zeros(n, dtype=np.int32)
-        for i, s in enumerate(seqs):
-            p = s.params
-            temps[i] = p.temperature if p.do_sample else 0.0
-            ks[i] = p.top_k if 0 < p.top_k <= self.K else self.K  # wider top_k: see _needs_full_vocab
-            ps[i] = p.top_p
-            seeds[i] = int(s.seed) & 0x7FFFFFFFFFFFFFFF
-            steps[i] = len(s.out)
-        return np.concatenate([seeds.view(np.int32), temps.view(np.int32), ps.view(np.int32), ks, steps])
-
-    @staticmethod
-    def _sampling_views(buf, n):
-        """(temps, ks, ps, seeds, steps) views of a packed int32 [6n] buffer (seeds first: 8-B aligned)."""
-        return (buf[2 * n:3 * n].view(torch.float32), buf[4 * n:5 * n], buf[3 * n:4 * n].view(torch.float32),
-                buf[0:2 * n].view(torch.int64), buf[5 * n:6 * n])
-
-    def _sampling_tensors(self, seqs, pad_to=None):
-        n = pad_to or len(seqs)
-        buf = self._h2d_i32(self._sampling_host(seqs, pad_to))
-        return self._sampling_views(buf, n)
-
     def _needs_full_vocab(self, seqs):
         """True if a sampled request's top_k does not fit the K-wide candidate lists (top_k = 0 means
         "disabled" as in transformers' TopKLogitsWarper, top_k > K): such a step samples from the full
@@ -710,13 +625,13 @@ class LLMEngine:
             self._warned_topk = True
         return bad
 
-    def _sample_full_vocab(self, logits, seqs, proc=None, want_lp=False):
+    def _sample_full_vocab(self, logits, seqs, proc=None):
         """Exact temperature -> top-k (if 0 < top_k) -> top-p -> multinomial over the whole vocabulary
         (transformers' LogitsProcessor order, [dep] generation/utils.py:1311-1322). Under TP the vocab
         shards are all-gathered first. Uniforms come from torch.Generator(seed * 1000003 + step), as in
-        the torch backend's sampler. `proc`: the logit processors' argument block (_proc_tensors), applied
-        first, on this rank's shard. want_lp: also return the per-sequence logprob values (_lp_values' form)
-        of the rows that ask, computed from the gathered fp32 row with the reference functions."""
+        the torch backend's sampler. `proc`: the logit processors' argument block (_apply_processors), applied
+        first, on this rank's shard. Returns (tokens, the per-sequence logprob values in _lp_values' form of the
+        rows that ask, computed from the gathered fp32 row with the reference functions; None if no row asks)."""
         w = self.model.w
         if proc is not None:
             self._apply_processors(logits[:, :w.vocab_valid] if w.vocab_valid < logits.shape[1] else logits, proc)
@@ -760,8 +675,8 @@ class LLMEngine:
             u = float(torch.rand(1, generator=g)) * float(c[-1])
             j = min(int(torch.searchsorted(c, torch.tensor([u]), right=True)[0]), int(keep.sum()) - 1)
             toks.append(int(order[j]))
-        if not want_lp:
-            return toks
+        if not any(s.logprobs is not None for s in seqs):
+            return toks, None
         from ..ops import reference as R
 
         vals = []
@@ -779,8 +694,9 @@ class LLMEngine:
             vals.append((float(tl[0]), [(int(ti[0, j]), float(tp[0, j])) for j in range(k)]))
         return toks, vals
 
-    def _sample_rows(self, logits, temps, ks, ps, seeds, steps, out=None, proc=None, lp=None):
-        """`proc` (optional): the logit processors' argument block; their kernel then runs in place on the
+    def _sample_rows(self, logits, v, out=None, proc=None, lp=None):
+        """v: the views of the step block (its sampling section is read here).
+        `proc` (optional): the logit processors' argument block; their kernel then runs in place on the
         logits before the candidate top-k (temperature / top-k / top-p follow, as in transformers).
         `lp` (optional): the logprob block (nlp [B] on the device, buf = the output words of _lp_views): two
         more launches, lse_partials next to the top-k on the same logits view and logprobs_finish after the
@@ -812,7 +728,7 @@ class LLMEngine:
             cv, ci = self._gather_candidates(cv, ci)
             if part is not None:
                 part = self._gather_partials(part)
-        tok = be.sample_candidates(cv, ci, temps, ks, ps, seeds, steps, list_len=self.K)
+        tok = be.sample_candidates(cv, ci, v["temps"], v["top_k"], v["top_p"], v["seeds"], v["steps"], list_len=self.K)
         if lp is not None:
             o_lse, o_tl, o_tp, o_ti = self._lp_views(lp["buf"], lp["n"])
             be.logprobs_finish(part, cv, ci, self.K, tok, lp["nlp"], o_lse, o_tl, o_tp, o_ti)
@@ -944,27 +860,22 @@ class LLMEngine:
             if logits is None:
                 m.hidden_states(inp)
         finished = []
-        # logit processors of the sampled rows: their history (prompt, or prompt + generated for a mixed
-        # step's decode rows) was completed by this step's scatter
-        proc = self._proc_tensors(out_seqs, [s.length - 1 for s in out_seqs], [len(s.out) for s in out_seqs]) \
-            if out_seqs else None
-        if proc is not None:
-            self.stats["logit_proc_steps"] += 1
-            self.stats["penalty_steps"] += int("gen_start" in proc)
-        # the first generated token's logprobs: the same two launches on this eager sampling call
         vals = None
-        if out_seqs and self._needs_full_vocab(out_seqs):
-            # the host computes the values there: no device block, only the step is counted
-            if any(s.logprobs is not None for s in out_seqs):
-                self.stats["logprob_steps"] += 1
-                tok, vals = self._sample_full_vocab(logits, out_seqs, proc=proc, want_lp=True)
+        if out_seqs:
+            full_vocab = self._needs_full_vocab(out_seqs)
+            n = len(out_seqs)
+            v = self._eager_block(out_seqs, self._step_key(out_seqs, full_vocab))
+            # logit processors of the sampled rows: their history (prompt, or prompt + generated for a mixed
+            # step's decode rows) was completed by this step's scatter, so the kernel stores no ids
+            proc = dict(v, ids=None) if "rows" in v else None
+            if full_vocab:
+                tok, vals = self._sample_full_vocab(logits, out_seqs, proc=proc)
             else:
-                tok = self._sample_full_vocab(logits, out_seqs, proc=proc)
-        elif out_seqs:
-            lp = self._lp_block(out_seqs)
-            tok = self._sample_rows(logits, *self._sampling_tensors(out_seqs), proc=proc, lp=lp).cpu().tolist()
-            if lp is not None:
-                vals = self._lp_values(lp["buf"].cpu(), lp["n"], out_seqs)
+                # the first generated token's logprobs: the same two launches on this eager sampling call
+                lp = self._lp_block(v, n)
+                tok = self._sample_rows(logits, v, proc=proc, lp=lp).cpu().tolist()
+                if lp is not None:
+                    vals = self._lp_values(lp["buf"].cpu(), n, out_seqs)
         else:
             tok = []
             if self.is_cuda:
@@ -1003,80 +914,43 @@ class LLMEngine:
             s._bt_np, s._bt_nb = row, nb
         return row
 
-    def _decode_inputs_host(self, seqs, B):
-        """Packed int32 metadata: ids[B] pos[B] slots[B] kv_lens[B] bt[B*maxb] (+ pad to even)."""
-        mb = self.max_blocks
-        n = len(seqs)
-        out = np.zeros(4 * B + B * mb + (4 * B + B * mb) % 2, dtype=np.int32)
-        ids, pos, slots, kvl = (out[i * B:(i + 1) * B] for i in range(4))
-        bt = out[4 * B:4 * B + B * mb].reshape(B, mb)
-        kvl[:] = 1  # padded rows: 1 scratch token in block 0
-        if n:
-            p = np.fromiter((s.length - 1 for s in seqs), dtype=np.int32, count=n)
-            ids[:n] = np.fromiter((s.token_at(int(q)) for s, q in zip(seqs, p)), dtype=np.int32, count=n)
-            bt[:n] = np.stack([self._bt_row(s, int(q) // BLOCK + 1) for s, q in zip(seqs, p)])
-            pos[:n] = p
-            slots[:n] = bt[np.arange(n), p // BLOCK] * BLOCK + p % BLOCK
-            kvl[:n] = p + 1
-        return out
-
-    def _decode_graph(self, B, with_processors=False, with_logprobs=False, with_penalties=False):
-        """Decode graph of batch bucket B, keyed (B, with_processors). The plain entry is what every step of
-        requests without logit processors replays; the processor variant (captured lazily, like any bucket)
-        adds the processor kernel between lm_head and the top-k and appends its per-row argument block to the
-        packed buffer. A step in which some row wants logprobs replays a further variant keyed
-        (B, with_processors, True): the two logprob launches around the sampler, the rows' alternative counts
-        (nlp) as the last B words of the packed buffer, and entry["lp"]["buf"] as the values' device buffer.
-        A step in which some row uses presence / frequency penalties or a logit_bias replays a variant of its
-        own, keyed (B, True, with_logprobs, True): the penalty form of the processor launch, PEN_WORDS more
-        words per row after the ban ids. The entries under the keys above are what they were without it."""
-        key = (B, bool(with_processors)) + ((True,) if with_logprobs else ())
-        if with_penalties:
-            with_processors = True
-            key = (B, True, bool(with_logprobs), True)
+    def _decode_graph(self, key):
+        """Decode graph of a GraphKey (bucket, processors, logprobs, penalties), captured lazily; the entries
+        already captured stay the objects they are. entry["layout"] is the StepLayout of its packed buffer
+        (ONE H2D copy per step), entry["views"] the named views the graph reads.
+        - The plain entry is what every step of requests without opt-in features replays, and the only one
+          warmup_graphs captures.
+        - processors: the processor kernel between lm_head and the top-k, its per-row arguments in the block.
+        - penalties (implies processors): the penalty form of that launch, four more words per row.
+        - logprobs: the two logprob launches around the sampler, the rows' alternative counts (nlp) in the
+          block, and entry["lp"]["buf"] as the values' device buffer."""
         if key in self.graphs:
             return self.graphs[key]
         from ..ops.native import decode_partitions
 
         m = self.model
         dev = self.device
-        mb = self.max_blocks
-        meta_n = 4 * B + B * mb + (4 * B + B * mb) % 2  # even: the sampling block holds int64 seeds
-        # ONE H2D copy per step: [decode metadata | sampling params (6B) | carry map (B)]
-        # (+ with processors: [history rows | penalty | n-gram size | ban count | ban ids (B x BAN_IDS_MAX)])
-        # (+ with logprobs: [alternatives per row (B)])
-        proc_n = (4 + BAN_IDS_MAX + (self.PEN_WORDS if with_penalties else 0)) * B if with_processors else 0
-        packed = torch.zeros(meta_n + 7 * B + proc_n + (B if with_logprobs else 0), dtype=torch.int32, device=dev)
-        ids, pos, slots, kvl = (packed[i * B:(i + 1) * B] for i in range(4))
-        carry = packed[meta_n + 6 * B:meta_n + 7 * B]
-        bt = packed[4 * B:4 * B + B * mb].view(B, mb)
+        B = key.bucket
+        layout = StepLayout(B, self.max_blocks, key.processors, key.penalties, key.logprobs)
+        packed = torch.zeros(layout.words, dtype=torch.int32, device=dev)
+        v = layout.views(packed)
+        kvl, carry = v["kv_lens"], v["carry"]
         pt, mp = decode_partitions(self.max_model_len, B, m.Hkv)
         ws_o = torch.empty((B, m.Hq, mp, m.D), dtype=torch.float32, device=dev) if mp > 1 else None
         ws_ml = torch.empty((B, m.Hq, mp, 2), dtype=torch.float32, device=dev) if mp > 1 else None
-        meta = AttnMeta("decode", kvl, bt, part_tiles=pt, max_parts=mp, ws_o=ws_o, ws_ml=ws_ml)
-        temps, ks, ps, seeds, steps = self._sampling_views(packed[meta_n:meta_n + 6 * B], B)
-        samp = dict(temps=temps, ks=ks, ps=ps, seeds=seeds, steps=steps)
+        meta = AttnMeta("decode", kvl, v["block_table"], part_tiles=pt, max_parts=mp, ws_o=ws_o, ws_ml=ws_ml)
         out_tok = self._tok_out[:B]
-        inp = StepInput(ids, pos, slots, meta, None, carry=carry, carry_src=self._tok_out)
-
-        proc = None
-        if with_processors:
-            # the kernel stores ids[b] (already resolved by the embedding kernel for carried rows) at
-            # hist[row][pos[b]] before it reads the row's history
-            proc = self._proc_views(packed[meta_n + 7 * B:meta_n + 7 * B + proc_n], B, penalties=with_penalties)
-            proc["ids"], proc["pos"] = ids, pos
-        lp = None
-        if with_logprobs:
-            lp = dict(nlp=packed[meta_n + 7 * B + proc_n:meta_n + 7 * B + proc_n + B], n=B,
-                      buf=torch.zeros(self.LP_WORDS * B, dtype=torch.int32, device=dev))
+        inp = StepInput(v["ids"], v["pos"], v["slots"], meta, None, carry=carry, carry_src=self._tok_out)
+        # the processor kernel stores ids[b] (already resolved by the embedding kernel for carried rows) at
+        # hist[row][pos[b]] before it reads the row's history
+        proc = v if key.processors else None
+        lp = self._lp_block(v, B)
 
         def run():
-            logits = m.forward(inp)
-            self._sample_rows(logits, samp["temps"], samp["ks"], samp["ps"], samp["seeds"], samp["steps"],
-                              out=out_tok, proc=proc, lp=lp)
+            self._sample_rows(m.forward(inp), v, out=out_tok, proc=proc, lp=lp)
 
-        entry = dict(packed=packed, samp=samp, out=out_tok, run=run, graph=None, meta=meta, inp=inp, proc=proc,
-                     lp=lp)
+        entry = dict(layout=layout, packed=packed, views=v, out=out_tok, run=run, graph=None, meta=meta, inp=inp,
+                     proc=proc, lp=lp)
         if self.use_graphs:
             kvl.fill_(1)  # scratch-only rows while capturing
             carry.fill_(-1)
@@ -1093,6 +967,11 @@ class LLMEngine:
                 for _ in range(2):
                     run()
             torch.cuda.current_stream(dev).wait_stream(s)
+            # Engines are reference cycles (graphs -> entry -> run -> engine), so a dead one keeps its captured
+            # graphs until the collector runs, and torch no longer collects before a capture. On ROCm a CUDAGraph's
+            # destructor synchronises the device, which is illegal inside a capture and aborts the process:
+            # collect now, so that no dead graph is left for a collection that starts inside the capture below.
+            gc.collect()
             g = torch.cuda.CUDAGraph()
             # captured on the warm-up stream: stream-keyed native state (the persistent decode MLP's
             # arrival counters, ops/native.py _me_workspace) was allocated by the warm-up runs above
@@ -1107,7 +986,7 @@ class LLMEngine:
         if not self.is_cuda:  # CPU plumbing: eager decode, nothing to capture
             return
         for b in sizes or self.buckets:
-            self._decode_graph(b)
+            self._decode_graph(graph_key(b))
         # tensor parallel: leave warm-up together. A rank still capturing (host-bound, seconds on a loaded
         # host) would otherwise keep the others' first collectives spinning in their bounded peer waits.
         grp = getattr(self.comm, "cpu_group", None)
@@ -1118,26 +997,6 @@ class LLMEngine:
             dist.barrier(group=grp)
 
     # ------------------------------------------------------------------ asynchronous decode
-    def _decode_inputs_async(self, seqs, B, carried):
-        """As _decode_inputs_host, for a step whose rows with carried[i] feed the previous step's
-        in-flight token (position = committed length; id patched on the device)."""
-        mb = self.max_blocks
-        n = len(seqs)
-        out = np.zeros(4 * B + B * mb + (4 * B + B * mb) % 2, dtype=np.int32)
-        ids, pos, slots, kvl = (out[i * B:(i + 1) * B] for i in range(4))
-        bt = out[4 * B:4 * B + B * mb].reshape(B, mb)
-        kvl[:] = 1
-        if n:
-            c = np.asarray(carried, dtype=np.int32)
-            p = np.fromiter((s.length - 1 for s in seqs), dtype=np.int32, count=n) + c
-            ids[:n] = np.fromiter((0 if ci else s.token_at(int(q)) for s, q, ci in zip(seqs, p, carried)),
-                                  dtype=np.int32, count=n)
-            bt[:n] = np.stack([self._bt_row(s, int(q) // BLOCK + 1) for s, q in zip(seqs, p)])
-            pos[:n] = p
-            slots[:n] = bt[np.arange(n), p // BLOCK] * BLOCK + p % BLOCK
-            kvl[:n] = p + 1
-        return out
-
     def _decode_async(self, ready):
         t0 = time.perf_counter()
         prev = self._inflight
@@ -1152,31 +1011,11 @@ class LLMEngine:
         if not seqs:
             return self._drain()
         n = len(seqs)
-        carried = [id(s) in prev_row for s in seqs]
-        B = self._bucket(n)
-        with_proc = any(s.hist_row >= 0 for s in seqs)
-        with_lp = any(s.logprobs is not None for s in seqs)
-        with_pen = with_proc and self._uses_penalties(seqs)
-        e = self._decode_graph(B, with_proc, with_lp, with_pen)
-        samp = self._sampling_host(seqs, pad_to=B)
-        steps = samp[5 * B:5 * B + n]
-        steps += np.asarray(carried, dtype=np.int32)  # sampling step index of the token being produced
+        key = self._step_key(seqs)
+        e = self._decode_graph(key)
         # carried rows read their id from the previous step's sampled tokens (the shared device buffer
         # _tok_out, row = that step's row) inside the graph's embedding kernel: no extra copy / gather
-        carry = np.full(B, -1, dtype=np.int32)
-        carry[:n] = [prev_row[id(s)] if c else -1 for s, c in zip(seqs, carried)]
-        parts = [self._decode_inputs_async(seqs, B, carried), samp, carry]
-        if with_proc:
-            # tokens generated before the one this step samples: a carried row's in-flight token counts, as
-            # in `steps` above
-            parts.append(self._proc_host(seqs, [len(s.out) + int(c) for s, c in zip(seqs, carried)], pad_to=B,
-                                         penalties=with_pen))
-            self.stats["logit_proc_steps"] += 1
-            self.stats["penalty_steps"] += int(with_pen)
-        if with_lp:
-            parts.append(self._lp_host(seqs, pad_to=B))
-            self.stats["logprob_steps"] += 1
-        host = np.concatenate(parts)
+        host = self._pack(e["layout"], seqs, [prev_row.get(id(s), -1) for s in seqs])
         e["packed"].copy_(self._h2d_i32(host), non_blocking=True)
         forced = self._engine_fault_hook()
         if self._timing is not None:
@@ -1193,14 +1032,14 @@ class LLMEngine:
         host_out = self._out_pins[self._out_idx]
         host_out[:n].copy_(e["out"][:n], non_blocking=True)
         lp_host = None
-        if with_lp:  # the step's logprob values ride to the host with its tokens: one more non-blocking copy
-            lp_host = self._lp_pin(self._out_idx, self.LP_WORDS * B)
+        if key.logprobs:  # the step's logprob values ride to the host with its tokens: one more non-blocking copy
+            lp_host = self._lp_pin(self._out_idx, self.LP_WORDS * key.bucket)
             lp_host.copy_(e["lp"]["buf"], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.device))
         for s in seqs:
             s.computed = s.length + (1 if id(s) in prev_row else 0)
-        cur = dict(seqs=seqs, out=e["out"], event=ev, host_out=host_out, n=n, lp_host=lp_host, B=B)
+        cur = dict(seqs=seqs, out=e["out"], event=ev, host_out=host_out, n=n, lp_host=lp_host, B=key.bucket)
         fin = self._collect(prev, in_flight=set(id(s) for s in seqs))
         if fin is None:  # prev failed in-kernel; cur consumed its tokens on the device
             self._recover_engine_fault([prev, cur])
@@ -1310,34 +1149,14 @@ class LLMEngine:
         finished = []
         if not seqs:
             return finished
-        gen = [len(s.out) for s in seqs]
-        with_proc = any(s.hist_row >= 0 for s in seqs)
-        with_pen = with_proc and self._uses_penalties(seqs)
-        if with_proc:
-            self.stats["logit_proc_steps"] += 1
-            self.stats["penalty_steps"] += int(with_pen)
-        with_lp = any(s.logprobs is not None for s in seqs)
+        key = self._step_key(seqs, full_vocab)
         vals = None
         if self.is_cuda:
-            B = self._bucket(n)
-            # a full-vocabulary step computes its logprobs on the host: it needs no graph variant
-            e = self._decode_graph(B, with_proc, with_lp and not full_vocab, with_pen)
-            parts = [self._decode_inputs_host(seqs, B), self._sampling_host(seqs, pad_to=B),
-                     np.full(B, -1, dtype=np.int32)]
-            if with_proc:
-                parts.append(self._proc_host(seqs, gen, pad_to=B, penalties=with_pen))
-            if with_lp and not full_vocab:
-                parts.append(self._lp_host(seqs, pad_to=B))
-            if with_lp:
-                self.stats["logprob_steps"] += 1
-            e["packed"].copy_(self._h2d_i32(np.concatenate(parts)), non_blocking=True)
+            e = self._decode_graph(key)
+            e["packed"].copy_(self._h2d_i32(self._pack(e["layout"], seqs)), non_blocking=True)
             if full_vocab:  # eager forward, exact sampler over the whole vocabulary
-                proc = None
-                if with_proc:
-                    proc = {k: (v[:n] if v is not None else None) for k, v in e["proc"].items()}
-                tok = self._sample_full_vocab(self.model.forward(e["inp"])[:n], seqs, proc=proc, want_lp=with_lp)
-                if with_lp:
-                    tok, vals = tok
+                proc = {k: t[:n] for k, t in e["proc"].items()} if key.processors else None
+                tok, vals = self._sample_full_vocab(self.model.forward(e["inp"])[:n], seqs, proc=proc)
             else:
                 forced = self._engine_fault_hook()
                 if e["graph"] is not None:
@@ -1347,29 +1166,22 @@ class LLMEngine:
                 if forced:
                     self._engine_fault_hook(release=True)
                 tok = e["out"][:n].cpu().tolist()
-                if with_lp:
-                    vals = self._lp_values(e["lp"]["buf"].cpu(), B, seqs)
+                if key.logprobs:
+                    vals = self._lp_values(e["lp"]["buf"].cpu(), key.bucket, seqs)
             if self._kernel_fault():  # synchronised by the token read-back above
                 self._recover_engine_fault([dict(seqs=seqs)])
                 self.stats["decode_s"] += time.perf_counter() - t0
                 return finished
         else:
-            host = self._decode_inputs_host(seqs, n)
-            mb = self.max_blocks
-            t = torch.from_numpy(host)
-            kvl = t[3 * n:4 * n]
-            meta = AttnMeta("decode", kvl, t[4 * n:4 * n + n * mb].view(n, mb), host_kv_lens=kvl.tolist())
-            inp = StepInput(t[:n], t[n:2 * n], t[2 * n:3 * n], meta, None)
-            logits = self.model.forward(inp)
-            proc = self._proc_tensors(seqs, t[n:2 * n], gen, ids=t[:n]) if with_proc else None
+            v = self._eager_block(seqs, key, self.max_blocks)
+            meta = AttnMeta("decode", v["kv_lens"], v["block_table"], host_kv_lens=v["kv_lens"].tolist())
+            logits = self.model.forward(StepInput(v["ids"], v["pos"], v["slots"], meta, None))
+            proc = v if key.processors else None
             if full_vocab:
-                tok = self._sample_full_vocab(logits, seqs, proc=proc, want_lp=with_lp)
-                if with_lp:
-                    self.stats["logprob_steps"] += 1
-                    tok, vals = tok
+                tok, vals = self._sample_full_vocab(logits, seqs, proc=proc)
             else:
-                lp = self._lp_block(seqs)
-                tok = self._sample_rows(logits, *self._sampling_tensors(seqs), proc=proc, lp=lp).tolist()
+                lp = self._lp_block(v, n)
+                tok = self._sample_rows(logits, v, proc=proc, lp=lp).tolist()
                 if lp is not None:
                     vals = self._lp_values(lp["buf"], n, seqs)
             if self._kernel_fault():

@@ -220,7 +220,7 @@ def test_graph_eager_async_sync_identical(native, tiny_llama):
         outs[name] = _run_mixed(eng, prompts, params)
         assert eng.stats["logit_proc_steps"] > 0
         if name == "async":
-            assert any(k[1] for k in eng.graphs) and any(not k[1] for k in eng.graphs)
+            assert any(k.processors for k in eng.graphs) and any(not k.processors for k in eng.graphs)
             outs["again"] = _run_mixed(eng, prompts, params)
     assert outs["async"] == outs["sync"] == outs["eager"] == outs["again"]
     for (out, reason), pr, pa in zip(outs["async"], prompts, params):
@@ -296,12 +296,12 @@ def test_default_path_untouched_by_a_processor_request(native, tiny_llama):
     p = SamplingParams(max_new_tokens=8, temperature=0.8, top_p=0.9, top_k=40, ignore_eos=True)
     eng = _engine(cfg, sd, "cuda", True)
     a = eng.generate(prompts, p, seeds=[1, 2, 3])
-    assert eng.stats["logit_proc_steps"] == 0 and eng._hist is None and all(not k[1] for k in eng.graphs)
+    assert eng.stats["logit_proc_steps"] == 0 and eng._hist is None and all(not k.processors for k in eng.graphs)
     entries = {k: v for k, v in eng.graphs.items()}
     eng.generate(prompts[:2], SamplingParams(max_new_tokens=8, temperature=0.8, top_p=0.9, top_k=40, ignore_eos=True,
                                              repetition_penalty=1.3, no_repeat_ngram_size=2), seeds=[4, 5])
     n = eng.stats["logit_proc_steps"]
-    assert n > 0 and any(k[1] for k in eng.graphs)
+    assert n > 0 and any(k.processors for k in eng.graphs)
     b = eng.generate(prompts, p, seeds=[1, 2, 3])
     assert a == b and eng.stats["logit_proc_steps"] == n
     assert all(eng.graphs[k] is v for k, v in entries.items())

@@ -152,7 +152,8 @@ def test_graph_eager_async_sync_identical(native, tiny_llama):
         outs[name] = _run(eng, prompts, params)
         assert eng.stats["logprob_steps"] > 0
         if name == "async":
-            assert any(len(k) == 3 for k in eng.graphs) and any(len(k) == 2 for k in eng.graphs)
+            assert any(k.logprobs and not k.penalties for k in eng.graphs)
+            assert any(not (k.logprobs or k.penalties) for k in eng.graphs)
             outs["again"] = _run(eng, prompts, params)
     assert outs["async"] == outs["sync"] == outs["eager"] == outs["again"]
     assert any(r == "stop" for _, r, _, _ in outs["async"]) and any(r == "length" for _, r, _, _ in outs["async"])
@@ -222,15 +223,16 @@ def test_plain_path_untouched_by_a_logprobs_request(native, tiny_llama):
     eng = _engine(cfg, sd, "cuda", True)
     a = eng.generate(prompts, p, seeds=[1, 2, 3])
     a2 = eng.generate(prompts[:2], pen, seeds=[4, 5])
-    assert eng.stats["logprob_steps"] == 0 and eng._lp_pins is None and all(len(k) == 2 for k in eng.graphs)
-    assert any(k[1] for k in eng.graphs) and any(not k[1] for k in eng.graphs)
+    assert eng.stats["logprob_steps"] == 0 and eng._lp_pins is None
+    assert not any(k.logprobs or k.penalties for k in eng.graphs)
+    assert any(k.processors for k in eng.graphs) and any(not k.processors for k in eng.graphs)
     entries = dict(eng.graphs)
     lp = SamplingParams(max_new_tokens=8, temperature=0.8, top_p=0.9, top_k=40, ignore_eos=True, logprobs=2)
     seqs = [eng.add_request(pr, q, seed=sd_) for pr, q, sd_ in zip(prompts[:2], (lp, p), (4, 5))]
     eng.run_until_done()
     n = eng.stats["logprob_steps"]
     assert n == 8 and len(seqs[0].logprobs) == 8 and seqs[1].logprobs is None  # 1 prefill + 7 decode steps
-    assert any(len(k) == 3 and k[2] for k in eng.graphs)
+    assert any(k.logprobs and not k.penalties for k in eng.graphs)
     assert eng.generate(prompts, p, seeds=[1, 2, 3]) == a and eng.generate(prompts[:2], pen, seeds=[4, 5]) == a2
     assert eng.stats["logprob_steps"] == n
     assert all(eng.graphs[k] is v for k, v in entries.items())

@@ -355,7 +355,7 @@ def test_graph_eager_async_sync_identical(native, tiny_llama):
         outs[name] = _run_mixed(eng, prompts, params)
         assert 0 < eng.stats["penalty_steps"] <= eng.stats["logit_proc_steps"]
         if name == "async":
-            assert any(len(k) == 4 and k[3] for k in eng.graphs)  # the penalty variant was captured and replayed
+            assert any(k.penalties for k in eng.graphs)  # the penalty variant was captured and replayed
             outs["again"] = _run_mixed(eng, prompts, params)
     tok = {k: [(o, r) for o, r, _ in v] for k, v in outs.items()}
     assert tok["async"] == tok["sync"] == tok["eager"] == tok["again"]
@@ -460,16 +460,16 @@ def test_other_graph_variants_untouched_by_a_penalty_request(native, tiny_llama)
     eng = _engine(cfg, sd, "cuda", True)
     a = eng.generate(prompts, p, seeds=[1, 2, 3])
     b = eng.generate(prompts[:2], q, seeds=[4, 5])
-    assert eng.stats["penalty_steps"] == 0 and all(len(k) == 2 for k in eng.graphs)
-    assert {k[1] for k in eng.graphs} == {False, True}
+    assert eng.stats["penalty_steps"] == 0 and not any(k.logprobs or k.penalties for k in eng.graphs)
+    assert {k.processors for k in eng.graphs} == {False, True}
     entries = dict(eng.graphs)
     n_proc = eng.stats["logit_proc_steps"]
     eng.generate(prompts[:2], dataclasses.replace(q, frequency_penalty=1.0, logit_bias=((5, 1.0),)), seeds=[4, 5])
     eng.generate(prompts[:1], dataclasses.replace(p, presence_penalty=1.0, logprobs=2), seeds=[6])
     n_pen = eng.stats["penalty_steps"]
     new = set(eng.graphs) - set(entries)
-    assert n_pen >= 14 and new and all(len(k) == 4 and k[1] is True and k[3] is True for k in new)
-    assert {k[2] for k in new} == {False, True}
+    assert n_pen >= 14 and new and all(k.processors is True and k.penalties is True for k in new)
+    assert {k.logprobs for k in new} == {False, True}
     assert eng.stats["logit_proc_steps"] == n_proc + n_pen
     assert eng.generate(prompts, p, seeds=[1, 2, 3]) == a and eng.generate(prompts[:2], q, seeds=[4, 5]) == b
     assert eng.stats["penalty_steps"] == n_pen

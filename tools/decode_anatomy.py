@@ -21,11 +21,13 @@ def replay_probe(eng, B, mid):
     """Back-to-back replays of the B-bucket graph from the engine's current (mid-run) metadata: the GPU time
     of one decode step with no host work in between; DA_REPLAY_MODES=h2d,d2h,both,adv,sync,pipe,pipe_copy add
     the engine's per-step copies / waits around the replays."""
-    e = eng.graphs.get((B, False))
+    from rag_llm_k8s_amd.engine.step_layout import graph_key
+
+    e = eng.graphs.get(graph_key(B))
     if e is None or e["graph"] is None:
         return
     pk = e["packed"]
-    live = int((pk[3 * B:4 * B] > 1).sum())
+    live = int((e["views"]["kv_lens"] > 1).sum())
     e["graph"].replay()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -50,7 +52,8 @@ def replay_probe(eng, B, mid):
             if mode == "adv":
                 stg = torch.empty_like(pin).pin_memory()
                 stg.copy_(base)
-                stg[B:4 * B] += it + 1  # pos, slots, kv_lens (the rows stay inside their last block)
+                for name in ("pos", "slots", "kv_lens"):  # the rows stay inside their last block
+                    e["layout"].views(stg)[name] += it + 1
                 pk.copy_(stg.to(pk.device, non_blocking=True), non_blocking=True)
             e["graph"].replay()
             if mode in ("d2h", "both"):

@@ -26,6 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 def main():
     from rag_llm_k8s_amd import _build
     from rag_llm_k8s_amd.engine.llm_engine import LLMEngine, SamplingParams
+    from rag_llm_k8s_amd.engine.step_layout import graph_key
     from rag_llm_k8s_amd.models import llama as L
     from rag_llm_k8s_amd.parallel.comm import SingleRankTPComm
 
@@ -77,8 +78,8 @@ def main():
         for _ in range(max(1, steps // 2)):
             eng.step()
         torch.cuda.synchronize()
-        e = eng.graphs.get((B, False))
-        live = int((e["packed"][3 * B:4 * B] > 1).sum())
+        e = eng.graphs.get(graph_key(B))
+        live = int((e["views"]["kv_lens"] > 1).sum())
         e["graph"].replay()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
