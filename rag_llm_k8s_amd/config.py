@@ -59,7 +59,9 @@ class RagConfig:
     do_sample: Optional[bool] = None  # None -> generation_config.json (reference: model.generate defaults)
     seed: int = 0
     tp_size: int = 1
-    dtype: str = "bf16"  # bf16 | fp8 (e4m3 weights, per-row scales) | mxfp4 (OCP MXFP4 weights; opt-in, lossy)
+    # bf16 | fp8 (e4m3 weights, per-row scales) | mxfp4 (OCP MXFP4 weights; opt-in, lossy) | int4 (an AWQ / GPTQ
+    # checkpoint as published, or 4-bit round-to-nearest codes of a bf16 one; group size 128; opt-in, lossy)
+    dtype: str = "bf16"
     device: str = "auto"  # auto | cuda | cpu
     index_type: str = "flat"  # flat | ivf
     ivf_nlist: int = 1024

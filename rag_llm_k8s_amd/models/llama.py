@@ -24,6 +24,7 @@ import torch
 
 from ..ops.backend import AttnMeta, get_backend
 from ..ops.fp8 import FP8, alloc_fp8_kv, check_fp8_kv_head_dim, kv_cache_torch_dtype
+from ..ops.int4 import Int4Weight
 from ..ops.reference import pack_gate_up, rope_tables
 
 # decode batches up to this size run the down projection on the register-streaming GEMM (fused residual)
@@ -124,8 +125,10 @@ class LlamaWeights:
                     I=c.intermediate_size // tp, V=-(-c.vocab_size // tp))
 
     @classmethod
-    def from_hf(cls, cfg, get, device, tp_rank=0, tp_size=1, dtype=torch.bfloat16):
-        """`get(name, rows=None, cols=None)` returns (a slice of) an HF-named tensor."""
+    def from_hf(cls, cfg, get, device, tp_rank=0, tp_size=1, dtype=torch.bfloat16, quant=None):
+        """`get(name, rows=None, cols=None)` returns (a slice of) an HF-named tensor.
+        quant: None, or "awq" / "gptq" for a 4-bit integer checkpoint (ops/int4.py): the seven projections are
+        read from their qweight / qzeros / scales tensors into Int4Weight; embedding, norms and lm_head stay bf16."""
         w = cls(cfg, tp_rank, tp_size)
         g = w.geom()
         r = tp_rank
@@ -137,6 +140,12 @@ class LlamaWeights:
         w.embed = dev(get("model.embed_tokens.weight"))
         for i in range(cfg.num_hidden_layers):
             p = "model.layers.%d." % i
+            if quant is not None:
+                w.layers.append(dict(
+                    ln_in=dev(get(p + "input_layernorm.weight")),
+                    ln_post=dev(get(p + "post_attention_layernorm.weight")),
+                    **{k: v.to(device) for k, v in cls._int4_layer(get, p, quant, g, r).items()}))
+                continue
             q = get(p + "self_attn.q_proj.weight", rows=(r * Hq * D, (r + 1) * Hq * D))
             k = get(p + "self_attn.k_proj.weight", rows=(r * Hkv * D, (r + 1) * Hkv * D))
             v = get(p + "self_attn.v_proj.weight", rows=(r * Hkv * D, (r + 1) * Hkv * D))
@@ -157,20 +166,61 @@ class LlamaWeights:
         w.lm_head = dev(lm)
         w.vocab_offset = lo
         w.vocab_valid = hi - lo
+        if quant is not None:
+            w._int4_ready()
         return w
 
+    @staticmethod
+    def _int4_layer(get, p, quant, g, r):
+        """The four kernel-layout weights of one layer of an AWQ / GPTQ checkpoint, on the host. The int32 / fp16
+        tensors are read whole and untouched; the TP shard (rows, or a K range that is a multiple of 128) is cut
+        from the unpacked container, and qkv / gate-up are joined on codes and meta words."""
+        from ..ops import int4
+
+        def proj(name):
+            qw, qz, sc = (get("%s%s.%s" % (p, name, t)) for t in ("qweight", "qzeros", "scales"))
+            if quant == "awq":
+                return int4.unpack_awq(qw, qz, sc)
+            try:
+                g_idx = get("%s%s.g_idx" % (p, name))
+            except KeyError:
+                g_idx = None
+            return int4.unpack_gptq(qw, qz, sc, g_idx)
+
+        D, Hq, Hkv, I = g["D"], g["Hq"], g["Hkv"], g["I"]
+        kv = (r * Hkv * D, (r + 1) * Hkv * D)
+        qkv = proj("self_attn.q_proj").slice(rows=(r * Hq * D, (r + 1) * Hq * D)).cat_rows(
+            proj("self_attn.k_proj").slice(rows=kv), proj("self_attn.v_proj").slice(rows=kv))
+        gt = proj("mlp.gate_proj").slice(rows=(r * I, (r + 1) * I))
+        up = proj("mlp.up_proj").slice(rows=(r * I, (r + 1) * I))
+        return dict(wqkv=qkv, wo=proj("self_attn.o_proj").slice(cols=(r * Hq * D, (r + 1) * Hq * D)),
+                    wgu=int4.Int4Weight(pack_gate_up(gt.packed, up.packed), pack_gate_up(gt.meta, up.meta)),
+                    wdown=proj("mlp.down_proj").slice(cols=(r * I, (r + 1) * I)))
+
+    def _int4_ready(self):
+        """Int4 weights are in place: on the GPU, reserve the bf16 scratch of the M > 64 route for every weight
+        shape now (one layer's worth of bf16), so the KV cache is sized from what is left."""
+        self.dtype = "int4"
+        if self.layers and self.layers[0]["wqkv"].device.type == "cuda":
+            from ..ops import native
+
+            for wt in self.layers[0].values():
+                if isinstance(wt, Int4Weight):
+                    native.int4_scratch(wt.shape[0], wt.shape[1], wt.device)
+        return self
+
     @classmethod
-    def from_checkpoint(cls, path, cfg, device, tp_rank=0, tp_size=1):
+    def from_checkpoint(cls, path, cfg, device, tp_rank=0, tp_size=1, quant=None):
         from ..runtime.safetensors_io import CheckpointReader
 
         rd = CheckpointReader(path)
         try:
-            return cls.from_hf(cfg, rd.get, device, tp_rank, tp_size)
+            return cls.from_hf(cfg, rd.get, device, tp_rank, tp_size, quant=quant)
         finally:
             rd.close()
 
     @classmethod
-    def from_state_dict(cls, cfg, sd, device, tp_rank=0, tp_size=1):
+    def from_state_dict(cls, cfg, sd, device, tp_rank=0, tp_size=1, quant=None):
         def get(name, rows=None, cols=None):
             t = sd[name]
             if rows is not None:
@@ -179,7 +229,7 @@ class LlamaWeights:
                 t = t[:, cols[0]:cols[1]]
             return t
 
-        return cls.from_hf(cfg, get, device, tp_rank, tp_size)
+        return cls.from_hf(cfg, get, device, tp_rank, tp_size, quant=quant)
 
     @classmethod
     def random(cls, cfg, device, tp_rank=0, tp_size=1, seed=0, dtype=torch.bfloat16):
@@ -233,6 +283,17 @@ class LlamaWeights:
             self.lm_head = quantize_weight(self.lm_head)
         self.dtype = "mxfp4"
         return self
+
+    def quantize_int4(self):
+        """4-bit integer weights (ops/int4.py: asymmetric round-to-nearest, one fp16 scale and zero point per 128 k)
+        for every linear layer (qkv, o, packed gate/up, down). Embedding, norms and lm_head stay bf16. Works on a
+        TP shard like quantize_mxfp4. A calibrated AWQ / GPTQ checkpoint loads through from_hf(quant=) instead."""
+        from ..ops.int4 import quantize_weight
+
+        for L in self.layers:
+            for k in ("wqkv", "wo", "wgu", "wdown"):
+                L[k] = quantize_weight(L[k])
+        return self._int4_ready()
 
     def nbytes(self):
         t = [self.embed, self.norm, self.lm_head] + [v for l in self.layers for v in l.values()]

@@ -18,12 +18,14 @@ from typing import List, Optional
 import torch
 
 from . import reference as R
-from . import mxfp4
+from . import int4, mxfp4
 from .fp8 import Fp8KV, Fp8Weight, reference_linear
+from .int4 import Int4Weight
 from .mxfp4 import Mxfp4Weight
 
 KV_BLOCK = 64
-_QUANT = (Fp8Weight, Mxfp4Weight)  # weight containers the bf16-only decode fusions refuse
+_QUANT = (Fp8Weight, Mxfp4Weight, Int4Weight)  # weight containers the bf16-only decode fusions refuse
+_W4 = (Mxfp4Weight, Int4Weight)  # 4-bit containers: no split-K slabs either, the generic per-projection path runs
 
 
 @dataclass
@@ -57,6 +59,8 @@ class TorchBackend:
             y = reference_linear(x, w, bias, resid, epi=epi, out_f32=out_f32)
         elif isinstance(w, Mxfp4Weight):
             y = mxfp4.reference_linear(x, w, bias, resid, epi=epi, out_f32=out_f32)
+        elif isinstance(w, Int4Weight):
+            y = int4.reference_linear(x, w, bias, resid, epi=epi, out_f32=out_f32)
         else:
             y = R.linear(x, w, bias, resid, epi=epi, out_f32=out_f32)
         if out is not None:
@@ -133,10 +137,10 @@ class TorchBackend:
     enable_part = False  # the torch oracle runs the same dataflow when a test switches it on
 
     def part_ok(self, M, w):  # MXFP4 weights: no split-K slabs, the generic per-projection path runs
-        return self.enable_part and M <= 64 and not isinstance(w, Mxfp4Weight)
+        return self.enable_part and M <= 64 and not isinstance(w, _W4)
 
     def gemm_part(self, x, w):
-        wf = w.dequant() if isinstance(w, (Fp8Weight, Mxfp4Weight)) else w.float()
+        wf = w.dequant() if isinstance(w, _QUANT) else w.float()
         return (x.float() @ wf.t()).unsqueeze(0)
 
     def part_norm_ok(self, M, w):
@@ -320,6 +324,9 @@ class NativeBackend(TorchBackend):
             return self.n.gemm_fp8(x, w, bias=bias, resid=resid, epi=epi, out=out, out_f32=out_f32)
         if isinstance(w, Mxfp4Weight):
             return self.n.gemm_mxfp4(x, w, bias=bias, resid=resid, epi=epi, out=out, out_f32=out_f32)
+        if isinstance(w, Int4Weight):  # fused W4A16 up to 64 rows; above, dequant_int4 + the bf16 GEMM
+            route = self.n.gemm_int4 if x.shape[0] <= 64 else self.n.gemm_int4_prefill
+            return route(x, w, bias=bias, resid=resid, epi=epi, out=out, out_f32=out_f32)
         return self.n.gemm(x, w, bias=bias, resid=resid, epi=epi, out=out, out_f32=out_f32, m_tiles=m_tiles)
 
     def m_tiles_ok(self, M, w, epi="none"):
@@ -359,7 +366,7 @@ class NativeBackend(TorchBackend):
     enable_part = __import__("os").environ.get("RAGK_DECODE_PART", "1") == "1"
 
     def part_ok(self, M, w):
-        if not self.enable_part or M > 64 or isinstance(w, Mxfp4Weight):
+        if not self.enable_part or M > 64 or isinstance(w, _W4):
             return False
         return self.n.gemm_part_slabs(M, w.shape[0], w.shape[1])[1] > 0
 
@@ -416,7 +423,7 @@ class NativeBackend(TorchBackend):
         return self.n.gemm_splitk(x, w, nsplit, m_tiles=m_tiles)
 
     def part_merge_ok(self, M, meta: AttnMeta, w, Hq, D):
-        return (self.enable_part and D == 128 and not isinstance(w, Mxfp4Weight)
+        return (self.enable_part and D == 128 and not isinstance(w, _W4)
                 and self.n.gemm_part_merge_ok(M, w, Hq, meta.max_parts, meta.ws_o))
 
     def gemm_part_merge(self, attn_out, meta: AttnMeta, w, Hq):

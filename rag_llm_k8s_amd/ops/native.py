@@ -897,6 +897,84 @@ def gemm_mxfp4(x, w, bias=None, resid=None, epi="none", out=None, out_f32=False,
     return out
 
 
+# ----------------------------------------------------------------------------- int4 (AWQ / GPTQ) GEMM
+def _int4_operands(w):
+    w4, mw = w.packed, w.meta
+    _req(w4.dtype == torch.uint8 and w4.is_cuda and w4.dim() == 2 and w4.is_contiguous() and w4.shape[1] % 64 == 0
+         and w4.data_ptr() % 16 == 0, "int4 weight: contiguous uint8 [rows, K/2] with K % 128 == 0, 16-byte aligned")
+    K = 2 * w4.shape[1]
+    _req(mw.dtype == torch.int32 and mw.is_cuda and mw.is_contiguous() and mw.shape == (w4.shape[0], K // 128),
+         "int4 meta: contiguous int32 [rows, K/128]")
+    return w4, mw, K
+
+
+def gemm_int4(x, w, bias=None, resid=None, epi="none", out=None, out_f32=False):
+    """out[M,N] = epi(x[M,K] @ dequant(w)^T) for an :class:`ops.int4.Int4Weight` w (rows = N, or 2N packed
+    gate/up for epi='silu_mul'): the fused W4A16 decode kernel, M <= 64 only (NativeBackend.gemm routes larger
+    M through dequant_int4 and the bf16 GEMM)."""
+    from .fp8 import DEC_MAX_M
+
+    _bf16_2d(x, "x")
+    _al16(x, "x")
+    M, K = x.shape
+    _req(M <= DEC_MAX_M, "gemm_int4 is the decode kernel: M <= %d" % DEC_MAX_M)
+    w4, mw, Kw = _int4_operands(w)
+    _req(Kw == K, "int4 weight K %d != x K %d" % (Kw, K))
+    e = EPI[epi]
+    N = w4.shape[0] // 2 if epi == "silu_mul" else w4.shape[0]
+    if epi == "silu_mul":
+        _req(N % 64 == 0 and not out_f32, "silu_mul needs N % 64 == 0, bf16 out")
+    if "bias" in epi:
+        _req(bias is not None and bias.is_cuda and bias.dtype == torch.bfloat16 and bias.numel() == N
+             and bias.is_contiguous(), "bias bf16[N]")
+    if "resid" in epi:
+        _bf16_2d(resid, "resid")
+        _req(resid.shape == (M, N), "resid shape")
+    odt = torch.float32 if out_f32 else torch.bfloat16
+    out = torch.empty((M, N), dtype=odt, device=x.device) if out is None else out
+    _req(out.dtype == odt and out.shape == (M, N) and out.stride(1) == 1, "out shape/dtype")
+    if M == 0:
+        return out
+    ldr = resid.stride(0) if resid is not None else 0
+    check(_lib.lib().ragk_gemm_int4(x.data_ptr(), x.stride(0), w4.data_ptr(), w4.stride(0), mw.data_ptr(),
+                                    mw.stride(0), out.data_ptr(), out.stride(0), ptr(bias), ptr(resid), ldr, M, N, K,
+                                    e, int(out_f32), stream_ptr()), "ragk_gemm_int4")
+    return out
+
+
+def dequant_int4(w, out=None):
+    """Int4Weight -> bf16 [rows, K] = bf16(fp32(scale) * (code - zero)); `out` may be a row-pitched view."""
+    w4, mw, K = _int4_operands(w)
+    rows = w4.shape[0]
+    out = torch.empty((rows, K), dtype=torch.bfloat16, device=w4.device) if out is None else out
+    _bf16_2d(out, "out")
+    _req(out.shape == (rows, K), "out shape")
+    _req(out.data_ptr() % 16 == 0 and out.stride(0) % 8 == 0, "out: 16-byte aligned rows")
+    check(_lib.lib().ragk_dequant_int4(w4.data_ptr(), w4.stride(0), mw.data_ptr(), mw.stride(0), out.data_ptr(),
+                                       out.stride(0), rows, K, stream_ptr()), "ragk_dequant_int4")
+    return out
+
+
+_int4_scratch = {}  # (device, rows, K, stream) -> bf16 [rows, K]
+
+
+def int4_scratch(rows, K, device):
+    """The bf16 buffer the M > 64 route dequantizes a [rows, K] int4 weight into: one per shape and stream, so
+    one stream reuses it in stream order and a second stream (micro-batched TP prefill) gets its own.
+    LlamaWeights reserves the current stream's when the weights are made, before the KV cache is sized."""
+    key = (torch.device(device), rows, K, stream_ptr())
+    buf = _int4_scratch.get(key)
+    if buf is None:
+        buf = _int4_scratch[key] = torch.empty((rows, K), dtype=torch.bfloat16, device=device)
+    return buf
+
+
+def gemm_int4_prefill(x, w, **kw):
+    """M > 64: dequant_int4 into the scratch, then the bf16 GEMM with the caller's arguments."""
+    rows, K = w.shape
+    return gemm(x, dequant_int4(w, int4_scratch(rows, K, w.device)), **kw)
+
+
 # ----------------------------------------------------------------------------- norms
 def rmsnorm(x, w, eps, out=None, resid=None):
     _bf16_2d(x, "x")

@@ -45,8 +45,18 @@ def build_generator(cfg, device, tp_rank=0, tp_size=1, comm=None, tp_group=None)
     mcfg = _load_json(os.path.join(cfg.model_path, "config.json"))
     if mcfg is None:
         raise FileNotFoundError("no config.json under MODEL_PATH=%s" % cfg.model_path)
-    if cfg.dtype == "mxfp4" and mcfg.get("model_type", "llama") == "gpt2":
-        raise ValueError("DTYPE=mxfp4 covers Llama-family checkpoints only; this GPT-2 checkpoint serves DTYPE=bf16")
+    if cfg.dtype in ("mxfp4", "int4") and mcfg.get("model_type", "llama") == "gpt2":
+        raise ValueError("DTYPE=%s covers Llama-family checkpoints only; this GPT-2 checkpoint serves DTYPE=bf16"
+                         % cfg.dtype)
+    qc = mcfg.get("quantization_config")
+    quant = None
+    if qc is not None:  # an AWQ / GPTQ checkpoint: qweight / qzeros / scales tensors, no bf16 linear weights
+        if cfg.dtype != "int4":
+            raise ValueError("this checkpoint is quantized (quant_method %r) and has no bf16 linear weights: it loads "
+                             "under DTYPE=int4, not DTYPE=%s" % (qc.get("quant_method"), cfg.dtype))
+        from ..ops.int4 import check_quant_config
+
+        quant = check_quant_config(qc)
     gen = _load_json(os.path.join(cfg.model_path, "generation_config.json"), {})
     tok = Tokenizer(cfg.model_path)
     mt = mcfg.get("model_type", "llama")
@@ -62,11 +72,14 @@ def build_generator(cfg, device, tp_rank=0, tp_size=1, comm=None, tp_group=None)
         from ..models.llama import LlamaConfig, LlamaModel, LlamaWeights
 
         c = LlamaConfig.from_dict(mcfg)
-        w = LlamaWeights.from_checkpoint(cfg.model_path, c, device, tp_rank, tp_size)
+        w = LlamaWeights.from_checkpoint(cfg.model_path, c, device, tp_rank, tp_size, quant=quant)
         if cfg.dtype == "fp8":  # DTYPE=fp8: e4m3fn linear weights, per-row scales (BASELINE config 5)
             w.quantize_fp8()
         elif cfg.dtype == "mxfp4":  # DTYPE=mxfp4: OCP MXFP4 linear weights, applied to this rank's shard (opt-in, lossy)
             w.quantize_mxfp4()
+        elif cfg.dtype == "int4" and quant is None:  # DTYPE=int4 on a plain checkpoint: round-to-nearest 4-bit codes
+            w.quantize_int4()
+        if cfg.dtype in ("mxfp4", "int4"):
             if torch.device(device).type == "cuda":
                 torch.cuda.empty_cache()  # hand the bf16 originals back before kv_blocks_for reads the free HBM
         max_len = min(cfg.max_model_len, c.max_position_embeddings)

@@ -195,6 +195,10 @@ def build_workload(model="8b", embedder="minilm", n_chunks=10000, chunk_words=10
         w.quantize_mxfp4()
         if device.startswith("cuda"):
             torch.cuda.empty_cache()
+    elif dtype == "int4":  # 4-bit integer linear weights, one fp16 scale / zero point per 128 k (ops/int4.py)
+        w.quantize_int4()
+        if device.startswith("cuda"):
+            torch.cuda.empty_cache()
     m = L.LlamaModel(lcfg, w, device, comm=tp_comm, max_positions=max_model_len)
     blocks = kv_blocks or (max_batch * (-(-max_model_len // 64)) + 16)
     engine = LLMEngine(m, num_blocks=blocks, max_batch=max_batch, max_prefill_tokens=max_prefill_tokens,
